@@ -14,14 +14,24 @@ Secondary configs (BASELINE.json:8-10), same JSON contract:
   --model mlp         static 3-layer MLP (F -> 256 -> 256 -> 1), resident batch
   --model mlp_online  dynamic MLP: every step trains on a NEW mini-batch streamed host -> HBM
   --model cnn         the reference's own 1-D CNN (cnn.py:110-118), SGD-Nesterov, 65,536 windows
-The default invocation times all three AFTER the headline's timed region, then the same
+A plain invocation does only what the headline figure needs: set up, warm up, time exactly
+--steps steps, print the JSON line. With --full it also times all three secondaries AFTER
+the headline's timed region, then the same
 models at the submission API's own batches (cnn_b20, mlp_b256, mlp_online_b256: CNN 20
 windows, MLP / online MLP 256 rows; one-GPU runs only, by default: the K-steps-per-launch
 paths), and reports them
 in a nested "secondary" object of the same JSON line (each with its own steps, ms/step,
-rows/s, timed seconds); the headline "value" is the LSTM alone.
+rows/s, timed seconds), and adds the "parity" object (the 20-step trajectories against fp32
+torch on the same GPU); the headline "value" is the LSTM alone. --secondary LIST and
+--parity on|none choose among them under --full (without it they are refused).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--model ...]
+                    [--full] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path left its caller
+after the last step as DIR/<name>.npy (float32): the trained flat parameters, the last
+step's predictions, the run's mean loss. Inputs and initial weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no torchrun environment, this process (which never touches the GPU)
 starts `torch.distributed.run --nproc-per-node N` on itself and exits with its status; under
@@ -482,13 +492,30 @@ SMALL_SECONDARY = {"cnn_b20": ("cnn", 20), "mlp_b256": ("mlp", 256), "mlp_online
 
 
 def _auto_secondary(default_headline: bool, world: int) -> list:
-    """The configs a default invocation times after the headline: all of SECONDARY on one GPU;
+    """The configs a --full invocation times after the headline: all of SECONDARY on one GPU;
     under DP without the job-default ones (they show the one-GPU K-steps-per-launch paths; at
     DP they would time per-step launches behind a latency-bound all-reduce — pass them
     explicitly for that)."""
     if not default_headline:
         return []
     return [m for m in SECONDARY if world <= 1 or m not in SMALL_SECONDARY]
+
+
+def _select_extras(full: bool, secondary: str, parity: str, default_headline: bool, world: int, cpu: bool):
+    """(secondary configs, parity?) of this invocation. Everything besides the headline sits
+    behind --full: a plain run has neither, and naming one without --full is an error
+    (ValueError) rather than a silently shorter line."""
+    if secondary == "auto":
+        sec = _auto_secondary(default_headline and full, world)
+    else:
+        sec = [m for m in secondary.split(",") if m and m != "none"]
+        bad = [m for m in sec if m not in SECONDARY]
+        if bad:
+            raise ValueError(f"--secondary: unknown {bad}")
+    if not full and (sec or parity == "on"):
+        raise ValueError("--secondary / --parity on need --full")
+    par = full and not cpu and (parity == "on" or (parity == "auto" and default_headline))
+    return sec, par
 
 
 def _small_launch_steps(args) -> int:
@@ -499,6 +526,30 @@ def _small_launch_steps(args) -> int:
         return 256
     return max(1, min(args.steps, 256))
 CPU_BATCH = {"lstm": 256, "mlp": 8192, "mlp_online": 8192, "cnn": 1024}
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def _dump_outputs(path: str, arrays: dict) -> dict:
+    """--dump-outputs: every tensor of ``arrays`` as ``path/<name>.npy`` (float32, flat). When
+    they exceed DUMP_MAX_BYTES together, an array above its equal share is cut to a fixed
+    sample of that size (sorted indices drawn with seed 0: the same elements in every run).
+    Returns {name: [elements written, elements in the tensor]}."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // 4 // max(len(arrays), 1)
+    fits = sum(t.numel() for t in arrays.values()) * 4 <= DUMP_MAX_BYTES
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().reshape(-1).numpy()
+        n = a.size
+        if not fits and n > share:
+            a = a[np.sort(np.random.default_rng(0).choice(n, size=share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = [int(a.size), int(n)]
+    return written
 
 
 def _run_model(args, ctx):
@@ -593,15 +644,21 @@ def main() -> int:
     ap.add_argument("--host-pool", type=int, default=8, help="mlp_online: distinct pinned host batches cycled")
     ap.add_argument("--device", choices=["auto", "cpu"], default="auto",
                     help="cpu: rehearse the launch/timing/JSON contract on the fp32 reference over gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline too: the secondary configs and the fp32 parity "
+                         "trajectories (--secondary / --parity choose among them); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (trained parameters, predictions, "
+                         "mean loss) as DIR/<name>.npy, float32, <= 64 MB in all")
     ap.add_argument("--secondary", default="auto",
                     help="comma list of configs timed after the headline (mlp,mlp_online,cnn), 'none'; "
-                         "auto = all three after the default LSTM headline, none otherwise")
+                         "auto = with --full all three after the default LSTM headline, none otherwise")
     ap.add_argument("--secondary-min-s", type=float, default=None,
                     help="minimum timed window per secondary config (its steps are raised to reach it); "
                          "default 0.1 s on the GPU, 0 on the CPU rehearsal")
     ap.add_argument("--parity", choices=["auto", "on", "none"], default="auto",
                     help="after every timed region: 20-step Adam trajectory of the headline shape vs fp32 "
-                         "torch on the same GPU (auto = with the default headline)")
+                         "torch on the same GPU (auto = with --full and the default headline)")
     args = ap.parse_args()
     args.min_timed_s = 0.0  # the headline: exactly --steps
     if args.secondary_min_s is None:
@@ -612,13 +669,12 @@ def main() -> int:
             args.batch = CPU_BATCH[args.model]
     default_headline = args.model == "lstm" and (args.batch, args.seq, args.hidden, args.features) == (
         DEFAULT_BATCH["lstm"] if args.device != "cpu" else CPU_BATCH["lstm"], 64, 512, 16)
-    if args.secondary == "auto":
-        secondary = _auto_secondary(default_headline, max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))))
-    else:
-        secondary = [m for m in args.secondary.split(",") if m and m != "none"]
-        bad = [m for m in secondary if m not in SECONDARY]
-        if bad:
-            ap.error(f"--secondary: unknown {bad}")
+    try:
+        secondary, parity = _select_extras(args.full, args.secondary, args.parity, default_headline,
+                                           max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))),
+                                           args.device == "cpu")
+    except ValueError as e:
+        ap.error(str(e))
 
     bad = _diag_env()
     if bad:
@@ -662,6 +718,13 @@ def main() -> int:
     untimed = _LAST_TIMED["untimed"]
     gpu_state = _LAST_TIMED.get("gpu_state")
     assert steps == args.steps
+    dumped = None
+    if args.dump_outputs and ctx.is_main:
+        # what the timed path left its caller after the last timed step (nothing has run since)
+        arrays = {"params": eng.params, "loss": torch.tensor([loss])}
+        if isinstance(getattr(eng, "pred", None), torch.Tensor):
+            arrays["pred"] = eng.pred
+        dumped = _dump_outputs(args.dump_outputs, arrays)
     comm = _comm_ms(ctx, eng.grads)
     grad_mb = round(eng.grads.numel() * 4 / 2**20, 3)
     step_graph, comm_in_graph = bool(run.graphs), bool(run.captured_comm)
@@ -669,7 +732,7 @@ def main() -> int:
     del run, eng
     sec = _secondary(args, ctx, secondary) if secondary else None
     par = None
-    if not cpu and (args.parity == "on" or (args.parity == "auto" and default_headline)):
+    if parity:
         # numerics of the headline step, after every timed region (rank 0's GPU; the others wait)
         if ctx.is_main:
             import gc
@@ -746,6 +809,8 @@ def main() -> int:
             rec["secondary"] = sec
         if par is not None:
             rec["parity"] = par
+        if dumped is not None:
+            rec["dumped_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
         rec["env"] = _env_record()
         print(json.dumps(rec), flush=True)
     ctx.shutdown()

@@ -91,7 +91,8 @@ def test_bench_secondary_configs_dp2():
     entry per config with its own steps, ms/step, rows/s (whole-job aggregate) and timed
     seconds; the headline value stays the LSTM's."""
     B = 4
-    rec = _run(2, "lstm", ["--batch", str(B), "--seq", "6", "--hidden", "16", "--secondary", "mlp,mlp_online,cnn"])
+    rec = _run(2, "lstm", ["--batch", str(B), "--seq", "6", "--hidden", "16", "--full", "--secondary",
+                          "mlp,mlp_online,cnn"])
     assert rec["value"] == pytest.approx(B * 2 / (rec["ms_per_step"] / 1000.0), rel=1e-3)
     sec = rec["secondary"]
     assert set(sec) == {"mlp", "mlp_online", "cnn"}
@@ -146,13 +147,86 @@ def test_gpu_state_sampler_window_math():
 def test_bench_job_default_secondaries():
     """The submission API's own batches ride in the bench line too (CNN 20 windows, MLP and
     online MLP 256 rows): the secondary names map to (model, per-GPU batch)."""
-    rec = _run(1, "lstm", ["--batch", "4", "--seq", "6", "--hidden", "16", "--secondary",
+    rec = _run(1, "lstm", ["--batch", "4", "--seq", "6", "--hidden", "16", "--full", "--secondary",
                            "cnn_b20,mlp_b256,mlp_online_b256"])
     sec = rec["secondary"]
     assert set(sec) == {"cnn_b20", "mlp_b256", "mlp_online_b256"}
     assert sec["cnn_b20"]["per_gpu_batch"] == 20 and "cnn" in sec["cnn_b20"]["metric"]
     assert sec["mlp_b256"]["per_gpu_batch"] == 256 and sec["mlp_online_b256"]["per_gpu_batch"] == 256
     assert all(v["value"] > 0 for v in sec.values())
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_is_the_headline_alone():
+    """Everything besides the headline sits behind --full: a plain default run selects no
+    secondary config and no parity pass, --full selects what the default line used to carry, and
+    naming a secondary (or --parity on) without --full is refused, not silently dropped."""
+    bench = _bench_module()
+    assert bench._select_extras(False, "auto", "auto", True, 1, False) == ([], False)
+    assert bench._select_extras(True, "auto", "auto", True, 1, False) == (list(bench.SECONDARY), True)
+    assert bench._select_extras(True, "auto", "auto", True, 8, False) == (["mlp", "mlp_online", "cnn"], True)
+    assert bench._select_extras(True, "auto", "auto", False, 1, False) == ([], False)  # another --model / shape
+    assert bench._select_extras(True, "mlp,cnn", "none", True, 1, False) == (["mlp", "cnn"], False)
+    assert bench._select_extras(True, "none", "on", False, 1, False) == ([], True)
+    assert bench._select_extras(True, "auto", "on", True, 1, True) == (list(bench.SECONDARY), False)  # CPU rehearsal
+    assert bench._select_extras(False, "none", "none", True, 1, False) == ([], False)
+    for sec, par in (("mlp", "auto"), ("none", "on")):
+        with pytest.raises(ValueError, match="--full"):
+            bench._select_extras(False, sec, par, True, 1, False)
+    with pytest.raises(ValueError, match="unknown"):
+        bench._select_extras(True, "resnet", "auto", True, 1, False)
+    r = subprocess.run([sys.executable, "bench.py", "--device", "cpu", "--secondary", "mlp"], capture_output=True,
+                       text=True, env=dict(os.environ, CUDA_VISIBLE_DEVICES=""), cwd=ROOT, timeout=300)
+    assert r.returncode == 2 and not r.stdout.strip() and "--full" in r.stderr
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: what the timed step left its caller after the last of exactly --steps
+    steps, as float32 .npy files; the inputs and initial weights are seeded, so a second run
+    with the same arguments writes the same arrays (the fp32 CPU step is deterministic)."""
+    import numpy as np
+
+    outs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        rec = _run(1, "lstm", ["--batch", "4", "--seq", "6", "--hidden", "16", "--dump-outputs", str(d)])
+        assert rec["steps"] == 3 and "secondary" not in rec and "parity" not in rec
+        assert rec["dumped_outputs"]["dir"] == str(d)
+        arrs = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert {"params", "loss"} <= set(arrs) == set(rec["dumped_outputs"]["elements"])
+        for k, a in arrs.items():
+            assert a.dtype == np.float32 and a.ndim == 1 and np.isfinite(a).all(), k
+            assert rec["dumped_outputs"]["elements"][k] == [a.size, a.size]
+        assert arrs["loss"][0] == pytest.approx(rec["train_loss"], rel=1e-5, abs=1e-6)  # float32 / 6 decimals
+        outs.append(arrs)
+    assert outs[0]["params"].size == 4 * 16 * (16 + 16) + 2 * 4 * 16 + 16 + 1  # torch LSTM + linear head
+    for k in outs[0]:
+        np.testing.assert_array_equal(outs[0][k], outs[1][k])
+
+
+def test_dump_outputs_size_cap(tmp_path, monkeypatch):
+    """Past 64 MB in all, an array above its share is written as a fixed seeded sample."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 300)
+    big, small = torch.arange(1000.0), torch.arange(7.0)
+    for d in ("a", "b"):
+        w = bench._dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+        assert w == {"big": [150, 1000], "small": [7, 7]}
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.size == 150 and (np.diff(a) > 0).all()
+    np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())
 
 
 def test_small_launch_steps_and_dp_secondaries():

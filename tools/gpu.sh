@@ -1,7 +1,8 @@
 #!/bin/bash
 # One entry point for every GPU-box run (replaces the round-1 one-off gpu_*.sh scripts).
 #   tools/gpu.sh tests            GPU test tier (+ smoke)
-#   tools/gpu.sh bench [args]     bench.py for lstm, mlp, mlp_online (extra args passed through)
+#   tools/gpu.sh bench [args]     bench.py for lstm, mlp, mlp_online (extra args passed through;
+#                                 --full: the headline line with its secondary configs and parity)
 #   tools/gpu.sh prof TAG [args]  rocprofv3 kernel-trace --stats of bench.py -> gpurun_out/prof_TAG
 #   tools/gpu.sh pmc TAG "CTRS" [args]  one rocprofv3 --pmc pass (<= 8 SQ counters) -> gpurun_out/pmc_TAG
 #   tools/gpu.sh all              tests + smoke + the three benches
