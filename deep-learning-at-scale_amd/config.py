@@ -164,7 +164,12 @@ def parse_argv(model: str, argv) -> RunConfig:
     """argv excludes the program name (sys.argv[1:])."""
     if model not in MODEL_DEFAULTS:
         raise ValueError(f"unknown model {model!r}")
-    ns = build_parser(model).parse_args(list(argv))
+    return config_from_namespace(model, build_parser(model).parse_args(list(argv)))
+
+
+def config_from_namespace(model: str, ns) -> RunConfig:
+    """RunConfig from a parsed :func:`build_parser` namespace (a job that adds options of its own
+    to the parser, wellflow/predict.py, parses first and converts here)."""
     cfg = RunConfig(model=model, **MODEL_DEFAULTS[model])
     cfg.column_names, cfg.column_types = ns.columnNames, ns.columnTypes
     cfg.target, cfg.storage_path = ns.targetColumn, ns.storagePath

@@ -939,6 +939,54 @@ void transpose_cast_bf16(const at::Tensor& src, int64_t lds, int64_t rows, int64
                                  cur_stream());
 }
 
+// Feature assembly on the device (features.hip): codes int32 [C][N] + cont fp32 [Q][N] ->
+// out [N][ld], bf16 (ld = round_up(F, 8), the MLP input format) or fp32 (ld = F, the LSTM row
+// table). cat_off / cat_size int32 [C], mean / std fp32 [Q] (device); C = 0 or Q = 0: pass None.
+constexpr int64_t kAssembleMaxF = 512;
+
+void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
+                       c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
+                       c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t N, int64_t F,
+                       const at::Tensor& out) {
+  TORCH_CHECK(N >= 1, "assemble_features: no rows");
+  TORCH_CHECK(F >= 1 && F <= kAssembleMaxF, "assemble_features: F = ", F, " outside 1 .. ", kAssembleMaxF);
+  const bool has_c = codes.has_value() && codes->defined() && codes->numel() > 0;
+  const bool has_q = cont.has_value() && cont->defined() && cont->numel() > 0;
+  int64_t C = 0, Q = 0;
+  if (has_c) {
+    check_t(*codes, at::kInt, "codes");
+    TORCH_CHECK(codes->dim() == 2 && codes->size(1) == N, "assemble_features: codes must be [C][N]");
+    C = codes->size(0);
+  }
+  if (has_q) {
+    check_t(*cont, at::kFloat, "cont");
+    TORCH_CHECK(cont->dim() == 2 && cont->size(1) == N, "assemble_features: cont must be [Q][N]");
+    Q = cont->size(0);
+  }
+  TORCH_CHECK(Q <= F && C <= F, "assemble_features: more source columns than features");
+  const int* off = opt_ptr<int>(cat_off, at::kInt, "cat_off", C);
+  const int* size = opt_ptr<int>(cat_size, at::kInt, "cat_size", C);
+  const float* mu = opt_ptr<float>(mean, at::kFloat, "mean", Q);
+  const float* sd = opt_ptr<float>(stdv, at::kFloat, "std", Q);
+  TORCH_CHECK(C == 0 || (off != nullptr && size != nullptr), "assemble_features: cat_off / cat_size missing");
+  TORCH_CHECK(Q == 0 || (mu != nullptr && sd != nullptr), "assemble_features: mean / std missing");
+  const bool bf = out.scalar_type() == at::kBFloat16;
+  check_t(out, bf ? at::kBFloat16 : at::kFloat, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == N, "assemble_features: out must be [N][ld]");
+  const int64_t ld = out.size(1);
+  TORCH_CHECK(bf ? (ld == (F + 7) / 8 * 8) : (ld == F), "assemble_features: out width ", ld, " does not fit F = ", F,
+              bf ? " (bf16: round_up(F, 8))" : " (fp32: F)");
+  TORCH_CHECK(wf::assemble_features_lds_bytes((int)ld, bf) <= wf::kAssembleMaxLds, "assemble_features: LDS tile too large");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(out.device());
+  const int* cp = has_c ? codes->data_ptr<int>() : nullptr;
+  const float* xp = has_q ? cont->data_ptr<float>() : nullptr;
+  const bool ok = bf ? wf::launch_assemble_features_bf16(cp, xp, off, size, mu, sd, N, (int)C, (int)Q, (int)F, (int)ld,
+                                                         bfp(out), cur_stream())
+                     : wf::launch_assemble_features_f32(cp, xp, off, size, mu, sd, N, (int)C, (int)Q, (int)F, (int)ld,
+                                                        fp(out), cur_stream());
+  TORCH_CHECK(ok, "assemble_features: the launcher refused the shape");
+}
+
 void im2col1d(const at::Tensor& x, int64_t B, int64_t L, int64_t Cin, int64_t ksz, int64_t Kp,
               const at::Tensor& col) {
   check_t(x, at::kFloat, "x");
@@ -1251,6 +1299,7 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(gather_rows);
   WF_DEF(transpose_cast_bf16);
   WF_DEF(im2col1d);
+  WF_DEF(assemble_features);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
   m.def("cnn_fused_ok", &cnn_fused_ok);

@@ -1,0 +1,158 @@
+// wellflow — feature assembly on the device (gfx950): raw table columns -> engine input rows.
+//
+// A scoring job touches every row once, so building the engines' input on the host (numpy
+// one-hot blocks + concatenate + standardise, data/features.py FeaturePipeline._assemble) and
+// uploading the widened [N][F] matrix is its whole run time. This kernel takes the raw columns
+// (int32 label codes [C][N], fp32 continuous values [Q][N]) and writes
+//   * OutT = bf16_t, ld = round_up(F, 8): the MLP input format (NativeMLP.to_input_format),
+//     columns F .. ld-1 zero;
+//   * OutT = float,  ld = F: the LSTM row table that lstm_pack_x_win reads.
+// Row r: one-hot blocks in pipeline order (block c has a 1 at cat_off[c] + code when
+// code < cat_size[c], else stays zero: the dropped last category and unseen labels), then the Q
+// continuous values (x - mean) / std: an fp32 subtract and a correctly rounded fp32 divide (the
+// build passes no fast-math flag), so the result equals the host pipeline bit for bit.
+//
+// Shape. Source columns are column-major and the output is row-major, so a 256-thread
+// workgroup transposes one 64-row tile through LDS:
+//   1. zero the tile (the one-hot zeros and the padding columns);
+//   2. lane = row, wave = source column: a wave reads 64 consecutive rows of one column (one
+//      256-B segment, every source value read exactly once) and writes its element into the
+//      tile. The tile's row stride is Dp = D | 1 dwords (D = dwords per output row), odd, so the
+//      64 lanes of a continuous column hit 32 distinct banks per half-wave; the one-hot 1s land
+//      at data-dependent columns;
+//   3. the tile's rows are contiguous in the output (64 rows x ld x sizeof(OutT) is a multiple of
+//      256 B), so it leaves as a flat copy: 16 B per lane, consecutive lanes at consecutive
+//      addresses. A lane gathers its four dwords from the padded tile with ds_read_b32; the k-th
+//      read of lane l takes dword (k + l / 8) & 3, so lanes l, l + 8, l + 16, l + 24 (whose four
+//      dwords share four banks: 32 lanes x 4 dwords span the 32 banks four times) read four
+//      different banks at once: at most 2-3 addresses per bank where the row padding shifts a
+//      lane's dwords, against 4 in the unrotated order.
+// No atomics; plain vector stores; any N >= 1 (the tail tile copies rows x D dwords, the last
+// < 4 of them as single dwords); C = 0 or Q = 0 allowed; grid-stride over tiles.
+#include "common.h"
+#include "kernels.h"
+
+namespace wf {
+
+namespace {
+
+constexpr int kAsmRows = 64;      // rows per tile = one wave of lanes per source column
+constexpr int kAsmThreads = 256;
+
+template <typename OutT>
+struct AsmOut;
+template <>
+struct AsmOut<float> {
+  static __device__ __forceinline__ float cvt(float v) { return v; }
+};
+template <>
+struct AsmOut<bf16_t> {
+  static __device__ __forceinline__ bf16_t cvt(float v) { return f2bf(v); }  // RNE, as cast_bf16_kernel
+};
+
+}  // namespace
+
+template <typename OutT>
+__global__ __launch_bounds__(kAsmThreads) void assemble_features_kernel(
+    const int* __restrict__ codes, const float* __restrict__ cont, const int* __restrict__ cat_off,
+    const int* __restrict__ cat_size, const float* __restrict__ mean, const float* __restrict__ stdv, long N, int C,
+    int Q, int F, int ld, OutT* __restrict__ out) {
+  extern __shared__ unsigned asm_tile[];  // [kAsmRows][Dp] dwords
+  constexpr int EPD = 4 / (int)sizeof(OutT);  // elements per dword
+  const int D = ld / EPD;                     // dwords per output row (bf16: ld % 8 == 0)
+  const int Dp = D | 1;
+  const int Fc = F - Q;  // width of the one-hot part
+  OutT* const telem = reinterpret_cast<OutT*>(asm_tile);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: the column spec loads go scalar
+  const long ntiles = (N + kAsmRows - 1) / kAsmRows;
+  for (long tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+    const long row0 = tl * kAsmRows;
+    const int rows = (int)((N - row0) < (long)kAsmRows ? (N - row0) : (long)kAsmRows);
+    for (int i = tid; i < kAsmRows * Dp; i += kAsmThreads) asm_tile[i] = 0u;
+    __syncthreads();
+    if (lane < rows) {
+      OutT* const trow = telem + (long)lane * Dp * EPD;
+      for (int s = wave; s < C + Q; s += kAsmThreads / 64) {
+        if (s < C) {
+          const int code = codes[(long)s * N + row0 + lane];
+          const int col = cat_off[s] + code;
+          // col < Fc also when the block spec itself were wrong: never a write outside the row
+          if ((unsigned)code < (unsigned)cat_size[s] && (unsigned)col < (unsigned)Fc) trow[col] = AsmOut<OutT>::cvt(1.0f);
+        } else {
+          const int q = s - C;
+          trow[Fc + q] = AsmOut<OutT>::cvt((cont[(long)q * N + row0 + lane] - mean[q]) / stdv[q]);
+        }
+      }
+    }
+    __syncthreads();
+    const int tile_dw = rows * D;
+    unsigned* const gout = reinterpret_cast<unsigned*>(out + row0 * ld);  // 256-B aligned: row0 % 64 == 0
+    const int nchunk = tile_dw >> 2;
+    const int rot = (lane >> 3) & 3;
+    for (int ch = tid; ch < nchunk; ch += kAsmThreads) {
+      const int d0 = ch * 4;
+      const int r0 = d0 / D, c0 = d0 - r0 * D;
+      unsigned v0 = 0u, v1 = 0u, v2 = 0u, v3 = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int kk = (k + rot) & 3;
+        int r = r0, c = c0 + kk;
+        while (c >= D) {  // a float row of F % 4 != 0 dwords: the 16 B straddle rows
+          c -= D;
+          ++r;
+        }
+        const unsigned w = asm_tile[r * Dp + c];
+        v0 = kk == 0 ? w : v0;
+        v1 = kk == 1 ? w : v1;
+        v2 = kk == 2 ? w : v2;
+        v3 = kk == 3 ? w : v3;
+      }
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      *reinterpret_cast<u32x4*>(gout + d0) = u32x4{v0, v1, v2, v3};
+    }
+    for (int d = nchunk * 4 + tid; d < tile_dw; d += kAsmThreads) {  // tail tile of a float table only
+      const int r = d / D;
+      gout[d] = asm_tile[r * Dp + (d - r * D)];
+    }
+    __syncthreads();  // the next tile's zero fill overwrites what this copy reads
+  }
+}
+
+size_t assemble_features_lds_bytes(int ld, bool bf16_out) {
+  const int D = bf16_out ? ld / 2 : ld;
+  return (size_t)kAsmRows * (D | 1) * 4;
+}
+
+template <typename OutT>
+static bool launch_assemble(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
+                            const float* mean, const float* stdv, long N, int C, int Q, int F, int ld, OutT* out,
+                            hipStream_t s) {
+  const size_t lds = assemble_features_lds_bytes(ld, sizeof(OutT) == 2);
+  if (lds > kAssembleMaxLds) return false;
+  auto kern = assemble_features_kernel<OutT>;
+  if (lds > 48 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+          hipSuccess)
+    return false;
+  const long ntiles = (N + kAsmRows - 1) / kAsmRows;
+  // capped grid: 8 workgroups per CU of a 256-CU device keep ~0.5 MB of column reads in flight
+  const long grid = ntiles < 2048 ? ntiles : 2048;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kAsmThreads), lds, s, codes, cont, cat_off, cat_size, mean, stdv,
+                     N, C, Q, F, ld, out);
+  return true;
+}
+
+bool launch_assemble_features_bf16(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
+                                   const float* mean, const float* stdv, long N, int C, int Q, int F, int ld,
+                                   bf16_t* out, hipStream_t s) {
+  return launch_assemble<bf16_t>(codes, cont, cat_off, cat_size, mean, stdv, N, C, Q, F, ld, out, s);
+}
+
+bool launch_assemble_features_f32(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
+                                  const float* mean, const float* stdv, long N, int C, int Q, int F, int ld, float* out,
+                                  hipStream_t s) {
+  return launch_assemble<float>(codes, cont, cat_off, cat_size, mean, stdv, N, C, Q, F, ld, out, s);
+}
+
+}  // namespace wf

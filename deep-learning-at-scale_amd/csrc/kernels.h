@@ -273,4 +273,18 @@ void launch_transpose_cast_bf16(const float* src, long lds, int rows, int cols, 
 void launch_im2col1d(const float* x, int B, int L, int Cin, int ksz, int Lout, int Kp,
                      bf16_t* col, hipStream_t s);
 
+// ---- feature assembly (features.hip): raw columns -> engine input rows ----
+// codes int32 [C][N], cont fp32 [Q][N] -> out [N][ld]: one-hot blocks (a 1 at cat_off[c] + code
+// when code < cat_size[c]), then (cont - mean) / std; F = sum(cat_size) + Q <= ld, columns
+// F .. ld-1 zero. bf16: ld % 8 == 0 (the MLP input format); f32: the LSTM row table. The 64-row
+// LDS tile is 64 x (dwords per row | 1) x 4 bytes; false = it would not fit (not launched).
+constexpr size_t kAssembleMaxLds = 160 * 1024;
+size_t assemble_features_lds_bytes(int ld, bool bf16_out);
+bool launch_assemble_features_bf16(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
+                                   const float* mean, const float* stdv, long N, int C, int Q, int F, int ld,
+                                   bf16_t* out, hipStream_t s);
+bool launch_assemble_features_f32(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
+                                  const float* mean, const float* stdv, long N, int C, int Q, int F, int ld, float* out,
+                                  hipStream_t s);
+
 }  // namespace wf

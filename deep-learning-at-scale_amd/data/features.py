@@ -64,6 +64,42 @@ class StringIndexer:
             out[i] = j
         return out
 
+    def codes(self, values) -> np.ndarray:
+        """``transform`` as int32, vectorised: the label lookup runs over the UNIQUE values only
+        (unique + inverse), not once per row (a scoring job looks every row up exactly once)."""
+        if len(values) == 0:
+            return np.zeros(0, np.int32)
+        uniq = None
+        if isinstance(values, np.ndarray) and values.dtype.kind == "U":
+            strs = values.reshape(-1)
+        elif isinstance(values, np.ndarray) and values.dtype != object:
+            # numeric arrays: str() of the array's own scalars, as transform sees them
+            strs = np.array([str(v) for v in values.reshape(-1)])
+        else:  # object arrays / lists (what the CSV readers return): astype(str) is str() per element
+            strs = np.asarray(values, dtype=object).reshape(-1)
+            try:  # all-str columns (the readers' output): hash-based factorize, ~10x np.unique's sort
+                import pandas as pd
+
+                if pd.api.types.infer_dtype(strs, skipna=False) == "string":
+                    inv, uniq = pd.factorize(strs)
+            except ImportError:
+                pass
+            if uniq is None:
+                strs = strs.astype(str)
+        if uniq is None:
+            uniq, inv = np.unique(strs, return_inverse=True)
+        lut = {k: i for i, k in enumerate(self.labels)}
+        unk = len(self.labels)
+        m = np.empty(len(uniq), np.int32)
+        for i, u in enumerate(uniq):
+            j = lut.get(str(u))
+            if j is None:
+                if self.handle_invalid == "error":
+                    raise ValueError(f"unseen label {str(u)!r} in column {self.column!r}")
+                j = unk
+            m[i] = j
+        return m[inv.reshape(-1)]
+
     @property
     def num_categories(self) -> int:
         return len(self.labels) + (1 if self.handle_invalid != "error" else 0)
@@ -134,14 +170,18 @@ class FeaturePipeline:
             return y
         return ((y - self.y_mean) / self.y_std).astype(np.float32)
 
-    def transform(self, table: dict):
+    def features(self, table: dict) -> np.ndarray:
+        """X [n, F] alone (a table that is scored need not hold the target column)."""
         X = self._assemble(table)
         if self.standardize and self.mean is not None:
             nc = len(self.continuous)
             # one-hot blocks are left as 0/1; only continuous columns are scaled
             if nc:
                 X[:, -nc:] = (X[:, -nc:] - self.mean[-nc:]) / self.std[-nc:]
-        return X.astype(np.float32), self.target_values(table)
+        return X.astype(np.float32)
+
+    def transform(self, table: dict):
+        return self.features(table), self.target_values(table)
 
     def inverse_target(self, y):
         return y * self.y_std + self.y_mean if self.standardize_target else y
@@ -162,6 +202,79 @@ class FeaturePipeline:
             "standardize_target": self.standardize_target,
             "drop_last": self.drop_last,
         }
+
+    STATE_KEYS = ("target", "categorical", "mean", "std", "y_mean", "y_std", "standardize_target", "drop_last")
+
+    @classmethod
+    def from_state(cls, schema: Schema, state: dict | None, n_features: int | None = None) -> "FeaturePipeline":
+        """The inverse of :meth:`state` (a scoring job restores the pipeline a training job fitted
+        and saved in its .mdl). ``mean`` / ``std`` come back as float32, so ``transform`` does the
+        same fp32 arithmetic as the fitted pipeline (bit-identical through a JSON round trip).
+        ``n_features``: the input width of the model the state belongs to; a restored pipeline of
+        another width raises."""
+        if not isinstance(state, dict):
+            raise ValueError("no feature-pipeline state (the .mdl was written without 'features')")
+        missing = [k for k in cls.STATE_KEYS if k not in state]
+        if missing:
+            raise ValueError(f"feature-pipeline state lacks {missing}")
+        target = state["target"]
+        want = list(state["categorical"].keys())
+        have = schema.categorical(exclude=(target,))
+        for c in want:
+            if c not in have:
+                raise ValueError(f"categorical column {c!r} of the saved pipeline is not a categorical column of "
+                                 f"the schema (schema has {have})")
+        for c in have:
+            if c not in want:
+                raise ValueError(f"categorical column {c!r} of the schema is not in the saved pipeline "
+                                 f"(it was fitted on {want})")
+        pipe = cls(schema, target, standardize=state["mean"] is not None, drop_last=bool(state["drop_last"]),
+                   standardize_target=bool(state["standardize_target"]))
+        # indexers in the SAVED order: the order of the one-hot blocks the model was trained on
+        pipe.indexers = [StringIndexer(c, labels=[str(v) for v in state["categorical"][c]]) for c in want]
+        if state["mean"] is not None:
+            if state["std"] is None:
+                raise ValueError("feature-pipeline state has a mean but no std")
+            pipe.mean = np.asarray(state["mean"], dtype=np.float32)
+            pipe.std = np.asarray(state["std"], dtype=np.float32)
+            if len(pipe.mean) != pipe.n_features or len(pipe.std) != pipe.n_features:
+                raise ValueError(f"feature-pipeline state has {len(pipe.mean)} means / {len(pipe.std)} stds for "
+                                 f"{pipe.n_features} features (the schema's continuous columns differ from training)")
+        pipe.y_mean, pipe.y_std = float(state["y_mean"]), float(state["y_std"])
+        if n_features is not None and pipe.n_features != int(n_features):
+            raise ValueError(f"the restored pipeline makes {pipe.n_features} features but the model's first layer "
+                             f"takes {int(n_features)}")
+        return pipe
+
+    def block_spec(self):
+        """(cat_off [C], cat_size [C]) int32: where each indexer's one-hot block starts in a
+        feature row and how wide it is — ``one_hot``'s own rule (num_categories, drop_last)."""
+        size = np.asarray([max(ix.num_categories - (1 if self.drop_last else 0), 0) for ix in self.indexers],
+                          dtype=np.int32)
+        off = (np.cumsum(size) - size).astype(np.int32)
+        return off, size
+
+    def scale(self):
+        """(mean [Q], std [Q]) float32 of the continuous columns; 0 / 1 without standardisation."""
+        nc = len(self.continuous)
+        if self.standardize and self.mean is not None and nc:
+            return (np.ascontiguousarray(self.mean[-nc:], dtype=np.float32),
+                    np.ascontiguousarray(self.std[-nc:], dtype=np.float32))
+        return np.zeros(nc, np.float32), np.ones(nc, np.float32)
+
+    def raw_columns(self, table: dict):
+        """(codes int32 [C][N], cont float32 [Q][N]): the table's columns as the device assembly
+        kernel reads them (csrc/features.hip) — label codes per categorical column (unseen labels:
+        len(labels)), continuous columns cast to float32 (int columns included), no one-hot
+        widening and no standardisation on the host."""
+        n = len(table[self.schema.names[0]])
+        codes = np.empty((len(self.indexers), n), np.int32)
+        for k, ix in enumerate(self.indexers):
+            codes[k] = ix.codes(table[ix.column])
+        cont = np.empty((len(self.continuous), n), np.float32)
+        for k, c in enumerate(self.continuous):
+            cont[k] = np.asarray(table[c], dtype=np.float32)
+        return codes, cont
 
 
 def time_block_split(starts: np.ndarray, span: int, groups=None, weights=(0.64, 0.16, 0.2), seed: int = 42):

@@ -389,6 +389,21 @@ class NativeLSTM:
                    None, None, 0.0)
         return self.pred[:B]
 
+    def forward_windows(self, windows, rows: torch.Tensor) -> torch.Tensor:
+        """Predictions [B] of windows ``rows`` (int64 [B], device, B == the engine batch) of a
+        resident :class:`~wellflow.data.features.SeriesWindows`: the x-pack kernel reads them in
+        place from the row table (as the row-indexed training step does; no [B][T][F] gather),
+        then the forward steps and the head. A view of an internal buffer."""
+        B = self.B
+        assert rows.shape == (B,) and rows.dtype == torch.int64 and rows.device == self.params.device
+        assert windows.rows.shape[1] == self.F and windows.T == self.T
+        self._C.lstm_pack_x_win(windows.rows, windows.starts, rows, self.XH, *self._dims(B), not self._xh_const)
+        self._xh_const = True
+        self._forward_steps(B)
+        _, w_out, b_out = self.lay.views(self.params)
+        self._C.head_fwd(self._hT(B), self.lay.KA, B, self.H, w_out, b_out, None, self.pred, None, None, 0.0)
+        return self.pred
+
     def forward_backward(self, x, y: torch.Tensor, grad_scale: float,
                          zero_grads: bool = True, step: int = 0,
                          loss_into: torch.Tensor | None = None, rows: torch.Tensor | None = None) -> torch.Tensor:

@@ -2,6 +2,9 @@
 
 Model names: cnn, mlp, mlp_online, lstm, gilbert (same argv contract as the per-model
 scripts under "Artificial intelligence models/" and "Physical model/").
+
+``python -m wellflow.submit predict <model> columnNames columnTypes targetColumn storagePath dataPath``
+scores a CSV with the ``.mdl`` a training job saved (wellflow/predict.py).
 """
 import sys
 
@@ -13,6 +16,10 @@ def main(argv=None) -> int:
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
+    if argv[0] == "predict":  # score a CSV with a saved .mdl (wellflow/predict.py)
+        from .predict import main as predict_main
+
+        return predict_main(argv[1:])
     run_job(argv[0], argv[1:])
     return 0
 

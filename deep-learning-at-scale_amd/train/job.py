@@ -53,7 +53,10 @@ def _save_best(cfg, name, ref, prepared):
     def cb(trainer):
         registry.engine_to_reference(trainer.eng, ref)
         extra = {"epoch": trainer.epoch, "val_loss": trainer.history.val_loss[-1],
-                 "features": prepared.pipeline.state() if prepared.pipeline else None}
+                 "features": prepared.pipeline.state() if prepared.pipeline else None,
+                 # what a scoring job cannot read off the layer shapes (wellflow/predict.py)
+                 "job": {"seq_len": int(cfg.seq_len), "group_col": prepared.info.get("group_col", cfg.group_col),
+                         "hidden": int(cfg.hidden), "mlp_hidden": [int(h) for h in cfg.mlp_hidden]}}
         ckpt.save_mdl(cfg.mdl_path(name), name, registry.keras_layers(name, ref), extra)
     return cb
 
