@@ -65,6 +65,9 @@ class RunConfig:
     decay: float = 1e-6
     nesterov: bool = True
     weight_decay: float = 0.0
+    # Keras-0.x gradient clipping of both optimizers, 0 = off (`clip` above is the mae_clip loss bound)
+    clipnorm: float = 0.0
+    clipvalue: float = 0.0
     # model shapes
     hidden: int = 512            # LSTM hidden (BASELINE.json:11)
     seq_len: int = 64            # LSTM window (BASELINE.json:11)
@@ -140,6 +143,8 @@ def build_parser(model: str) -> argparse.ArgumentParser:
     ap.add_argument("--decay", type=float)
     ap.add_argument("--no-nesterov", dest="nesterov", action="store_false", default=None)
     ap.add_argument("--weight-decay", type=float, dest="weight_decay")
+    ap.add_argument("--clipnorm", type=float, help="scale the gradient to this global L2 norm when it is larger (0 = off)")
+    ap.add_argument("--clipvalue", type=float, help="clamp every gradient element to [-v, v] (0 = off)")
     ap.add_argument("--hidden", type=int)
     ap.add_argument("--seq-len", type=int, dest="seq_len")
     ap.add_argument("--mlp-hidden", type=_tuple_ints, dest="mlp_hidden")

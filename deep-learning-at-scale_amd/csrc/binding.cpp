@@ -406,10 +406,17 @@ bool lstm_backward_dw(const at::Tensor& WhhT, const at::Tensor& XH, const at::Te
   return false;
 }
 
+// The clipnorm state block of grad_clip_scale (csrc/elementwise.hip) as the fused updates take it;
+// none = no clipnorm. Every update binding has its earlier call shape as a second overload.
+const float* clip_state(const c10::optional<at::Tensor>& clip) {
+  return opt_ptr<float>(clip, at::kFloat, "clip", wf::kGradClipStateFloats);
+}
+
 // Adam on the LSTM's flat parameters + Wp / WhhT (lstm_pack_weights' output) in one launch
 void lstm_adam_pack(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
                     const at::Tensor& step, double lr, double b1, double b2, double eps, double wd, double gscale,
-                    bool zero_g, const at::Tensor& Wp, const at::Tensor& WhhT, int64_t H, int64_t KX) {
+                    bool zero_g, const at::Tensor& Wp, const at::Tensor& WhhT, int64_t H, int64_t KX,
+                    c10::optional<at::Tensor> clip, double clipvalue) {
   for (const at::Tensor* t : {&p, &g, &m, &v}) check_t(*t, at::kFloat, "p/g/m/v");
   const int64_t n = p.numel();
   TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "lstm_adam_pack: size mismatch");
@@ -425,7 +432,14 @@ void lstm_adam_pack(const at::Tensor& p, const at::Tensor& g, const at::Tensor& 
   TORCH_CHECK(reinterpret_cast<uintptr_t>(Wp.data_ptr()) % 8 == 0, "lstm_adam_pack: Wp must be 8-B aligned");
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
   wf::launch_lstm_adam_pack(fp(p), fp(g), fp(m), fp(v), n, fp(step), (float)lr, (float)b1, (float)b2, (float)eps,
-                            (float)wd, (float)gscale, zero_g ? 1 : 0, (int)KX, (int)H, bfp(Wp), bfp(WhhT), cur_stream());
+                            (float)wd, (float)gscale, zero_g ? 1 : 0, (int)KX, (int)H, bfp(Wp), bfp(WhhT), cur_stream(),
+                            clip_state(clip), (float)clipvalue);
+}
+void lstm_adam_pack_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
+                           const at::Tensor& step, double lr, double b1, double b2, double eps, double wd,
+                           double gscale, bool zero_g, const at::Tensor& Wp, const at::Tensor& WhhT, int64_t H,
+                           int64_t KX) {
+  lstm_adam_pack(p, g, m, v, step, lr, b1, b2, eps, wd, gscale, zero_g, Wp, WhhT, H, KX, c10::nullopt, 0.0);
 }
 
 void lstm_pack_weights(const at::Tensor& W, const at::Tensor& Wp, const at::Tensor& WhhT,
@@ -852,7 +866,8 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
 void adam_dev(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
               const at::Tensor& step, double lr, double b1, double b2, double eps, double wd,
               double gscale, c10::optional<at::Tensor> shadow, bool zero_g,
-              c10::optional<at::Tensor> shadow_t, int64_t t_off, int64_t t_rows, int64_t t_cols) {
+              c10::optional<at::Tensor> shadow_t, int64_t t_off, int64_t t_rows, int64_t t_cols,
+              c10::optional<at::Tensor> clip, double clipvalue) {
   check_t(p, at::kFloat, "p");
   check_t(g, at::kFloat, "g");
   check_t(m, at::kFloat, "m");
@@ -873,7 +888,15 @@ void adam_dev(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, con
   }
   wf::launch_adam_dev(fp(p), fp(g), fp(m), fp(v), n, fp(step), (float)lr, (float)b1, (float)b2,
                       (float)eps, (float)wd, (float)gscale, opt_ptr<bf16_t>(shadow, at::kBFloat16, "shadow", n),
-                      zero_g ? 1 : 0, cur_stream(), tdst, (long)t_off, (int)t_rows, (int)t_cols);
+                      zero_g ? 1 : 0, cur_stream(), tdst, (long)t_off, (int)t_rows, (int)t_cols, clip_state(clip),
+                      (float)clipvalue);
+}
+void adam_dev_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
+                     const at::Tensor& step, double lr, double b1, double b2, double eps, double wd, double gscale,
+                     c10::optional<at::Tensor> shadow, bool zero_g, c10::optional<at::Tensor> shadow_t, int64_t t_off,
+                     int64_t t_rows, int64_t t_cols) {
+  adam_dev(p, g, m, v, step, lr, b1, b2, eps, wd, gscale, shadow, zero_g, shadow_t, t_off, t_rows, t_cols,
+           c10::nullopt, 0.0);
 }
 
 void sgd(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, double lr,
@@ -889,7 +912,8 @@ void sgd(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, double
 }
 
 void sgd_dev(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, const at::Tensor& step, double lr,
-             double decay, double momentum, bool nesterov, double gscale, bool zero_g) {
+             double decay, double momentum, bool nesterov, double gscale, bool zero_g,
+             c10::optional<at::Tensor> clip, double clipvalue) {
   check_t(p, at::kFloat, "p");
   check_t(g, at::kFloat, "g");
   check_t(vel, at::kFloat, "vel");
@@ -899,7 +923,24 @@ void sgd_dev(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, co
   TORCH_CHECK(g.numel() == n && vel.numel() == n, "sgd: size mismatch");
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
   wf::launch_sgd_dev(fp(p), fp(g), fp(vel), n, fp(step), (float)lr, (float)decay, (float)momentum, nesterov ? 1 : 0,
-                     (float)gscale, zero_g ? 1 : 0, cur_stream());
+                     (float)gscale, zero_g ? 1 : 0, cur_stream(), clip_state(clip), (float)clipvalue);
+}
+void sgd_dev_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, const at::Tensor& step, double lr,
+                    double decay, double momentum, bool nesterov, double gscale, bool zero_g) {
+  sgd_dev(p, g, vel, step, lr, decay, momentum, nesterov, gscale, zero_g, c10::nullopt, 0.0);
+}
+
+// clipnorm: norm of gscale * g and the factor min(1, clipnorm / norm) into `state` (device only)
+void grad_clip_scale(const at::Tensor& g, double gscale, double clipnorm, const at::Tensor& partial,
+                     const at::Tensor& state) {
+  check_t(g, at::kFloat, "g");
+  check_t(partial, at::kFloat, "partial");
+  check_t(state, at::kFloat, "state");
+  check_extent(partial, wf::kGradClipMaxBlocks, "partial");
+  check_extent(state, wf::kGradClipStateFloats, "state");
+  TORCH_CHECK(g.numel() >= 1, "grad_clip_scale: empty bucket");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
+  wf::launch_grad_clip_scale(fp(g), g.numel(), (float)gscale, (float)clipnorm, fp(partial), fp(state), cur_stream());
 }
 
 void cast_bf16(const at::Tensor& src, const at::Tensor& dst) {
@@ -1124,7 +1165,8 @@ void cnn_pack(const at::Tensor& Wc, const at::Tensor& Wd, const std::vector<int6
 // Keras SGD on the CNN's flat parameters + the bf16 operand images (cnn_pack's output) in one launch
 void cnn_sgd_pack(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, const at::Tensor& step, double lr,
                   double decay, double momentum, bool nesterov, double gscale, bool zero_g,
-                  const std::vector<int64_t>& dims, const at::Tensor& WcA, const at::Tensor& WdF, const at::Tensor& WdB) {
+                  const std::vector<int64_t>& dims, const at::Tensor& WcA, const at::Tensor& WdF, const at::Tensor& WdB,
+                  c10::optional<at::Tensor> clip, double clipvalue) {
   auto d = cnn_checked(dims, 0.0);
   for (const at::Tensor* t : {&p, &g, &vel}) check_t(*t, at::kFloat, "p/g/vel");
   const int64_t n = p.numel();
@@ -1140,7 +1182,14 @@ void cnn_sgd_pack(const at::Tensor& p, const at::Tensor& g, const at::Tensor& ve
   }
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
   wf::launch_cnn_sgd_pack(fp(p), fp(g), fp(vel), n, fp(step), (float)lr, (float)decay, (float)momentum, nesterov ? 1 : 0,
-                          (float)gscale, zero_g ? 1 : 0, d, bfp(WcA), bfp(WdF), bfp(WdB), cur_stream());
+                          (float)gscale, zero_g ? 1 : 0, d, bfp(WcA), bfp(WdF), bfp(WdB), cur_stream(), clip_state(clip),
+                          (float)clipvalue);
+}
+void cnn_sgd_pack_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, const at::Tensor& step,
+                         double lr, double decay, double momentum, bool nesterov, double gscale, bool zero_g,
+                         const std::vector<int64_t>& dims, const at::Tensor& WcA, const at::Tensor& WdF,
+                         const at::Tensor& WdB) {
+  cnn_sgd_pack(p, g, vel, step, lr, decay, momentum, nesterov, gscale, zero_g, dims, WcA, WdF, WdB, c10::nullopt, 0.0);
 }
 
 static const long long* rng_ptr(const c10::optional<at::Tensor>& rng) {
@@ -1264,6 +1313,8 @@ struct Checked<F> {
 }  // namespace
 
 #define WF_DEF(name) m.def(#name, &Checked<&name>::call)
+// a second overload of `name`: the call shape from before the trailing clip arguments
+#define WF_DEF_AS(name, fn) m.def(#name, &Checked<&fn>::call)
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "wellflow HIP kernel library (gfx950)";
@@ -1286,6 +1337,7 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(lstm_backward_dw);
   WF_DEF(lstm_pack_weights);
   WF_DEF(lstm_adam_pack);
+  WF_DEF_AS(lstm_adam_pack, lstm_adam_pack_noclip);
   WF_DEF(head_fwd);
   WF_DEF(head_bwd_w);
   WF_DEF(head_fwd_bwd);
@@ -1293,8 +1345,11 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(loss);
   WF_DEF(adam);
   WF_DEF(adam_dev);
+  WF_DEF_AS(adam_dev, adam_dev_noclip);
   WF_DEF(sgd);
   WF_DEF(sgd_dev);
+  WF_DEF_AS(sgd_dev, sgd_dev_noclip);
+  WF_DEF(grad_clip_scale);
   WF_DEF(cast_bf16);
   WF_DEF(gather_rows);
   WF_DEF(transpose_cast_bf16);
@@ -1306,6 +1361,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("cnn_part_sizes", &cnn_part_sizes);
   WF_DEF(cnn_pack);
   WF_DEF(cnn_sgd_pack);
+  WF_DEF_AS(cnn_sgd_pack, cnn_sgd_pack_noclip);
   WF_DEF(cnn_forward);
   WF_DEF(cnn_backward);
   WF_DEF(cnn_reduce);

@@ -695,13 +695,15 @@ __global__ __launch_bounds__(256) void cnn_sgd_pack_kernel(float* __restrict__ p
                                                            float lr, float decay, float momentum, int nesterov,
                                                            float gscale, int zero_g, int T, int Fp, int NFB, int Kc,
                                                            int O, bf16_t* __restrict__ WcA, bf16_t* __restrict__ WdF,
-                                                           bf16_t* __restrict__ WdB) {
+                                                           bf16_t* __restrict__ WdB, const float* __restrict__ clip,
+                                                           float cv) {
   const float it = step[0];
+  const float gs = clip_gscale(gscale, clip);
   const float lr_t = lr / (1.f + decay * it);
   const long nc = (long)Fp * Kc, nf = (long)T * Fp, nd = 16 * nf;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gi = g[i] * gscale;
+    const float gi = clip_grad(g[i], gs, cv);
     const float v = momentum * vel[i] - lr_t * gi;
     vel[i] = v;
     const float pn = p[i] + (nesterov ? (momentum * v - lr_t * gi) : v);
@@ -766,12 +768,13 @@ void launch_cnn_pack(const float* Wc, const float* Wd, const CnnDims& d, bf16_t*
 
 void launch_cnn_sgd_pack(float* p, float* g, float* vel, long n, float* step, float lr, float decay, float momentum,
                          int nesterov, float gscale, int zero_g, const CnnDims& d, bf16_t* WcA, bf16_t* WdF,
-                         bf16_t* WdB, hipStream_t s) {
+                         bf16_t* WdB, hipStream_t s, const float* clip, float clipvalue) {
   long b = (n + 255) / 256;
   if (b > 2048) b = 2048;
   if (b < 1) b = 1;
   hipLaunchKernelGGL(cnn_sgd_pack_kernel, dim3((int)b), dim3(256), 0, s, p, g, vel, n, step, lr, decay, momentum,
-                     nesterov, gscale, zero_g, d.T, d.Fp, d.Fp / 16, d.Kc, d.O, WcA, WdF, WdB);
+                     nesterov, gscale, zero_g, d.T, d.Fp, d.Fp / 16, d.Kc, d.O, WcA, WdF, WdB, clip,
+                     clipvalue);
 }
 
 void launch_cnn_forward(const float* x, int B, const CnnDims& d, const bf16_t* WcA, const bf16_t* WdF,

@@ -88,6 +88,19 @@ __device__ __forceinline__ float uniform_hash(unsigned long long seed, unsigned 
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+// Gradient clipping as the fused optimizers apply it (Keras 0.x Optimizer.get_gradients):
+// gs = grad_scale * the clipnorm factor of grad_clip_scale_kernel (elementwise.hip), then the
+// clipvalue clamp to [-cv, cv] when cv > 0 (a NaN stays NaN, as torch.clamp keeps it).
+// `clip` is that kernel's state block; null = no clipnorm, and nothing is read.
+__device__ __forceinline__ float clip_gscale(float gscale, const float* clip) {
+  return clip != nullptr ? gscale * clip[0] : gscale;
+}
+__device__ __forceinline__ float clip_grad(float g, float gs, float cv) {
+  float x = g * gs;
+  if (cv > 0.f) x = x > cv ? cv : (x < -cv ? -cv : x);
+  return x;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -441,8 +441,10 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, fl
                                                        long n, float* __restrict__ step, float lr,
                                                        float b1, float b2, float eps, float wd,
                                                        float gscale, bf16_t* __restrict__ shadow, int zero_g,
-                                                       bf16_t* __restrict__ tdst, long t_off, int t_rows, int t_cols) {
+                                                       bf16_t* __restrict__ tdst, long t_off, int t_rows, int t_cols,
+                                                       const float* __restrict__ clip, float cv) {
   const float t = step[0] + 1.f;
+  const float gs = clip_gscale(gscale, clip);
   const float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   const long n4 = n / 4;
   const long stride = (long)gridDim.x * blockDim.x;
@@ -451,10 +453,10 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, fl
     float4 gg = reinterpret_cast<const float4*>(g)[i];
     float4 mm = reinterpret_cast<float4*>(m)[i];
     float4 vv = reinterpret_cast<float4*>(v)[i];
-    adam_one(pp.x, gg.x * gscale, mm.x, vv.x, lr, b1, b2, eps, wd, bc1, bc2);
-    adam_one(pp.y, gg.y * gscale, mm.y, vv.y, lr, b1, b2, eps, wd, bc1, bc2);
-    adam_one(pp.z, gg.z * gscale, mm.z, vv.z, lr, b1, b2, eps, wd, bc1, bc2);
-    adam_one(pp.w, gg.w * gscale, mm.w, vv.w, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.x, clip_grad(gg.x, gs, cv), mm.x, vv.x, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.y, clip_grad(gg.y, gs, cv), mm.y, vv.y, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.z, clip_grad(gg.z, gs, cv), mm.z, vv.z, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.w, clip_grad(gg.w, gs, cv), mm.w, vv.w, lr, b1, b2, eps, wd, bc1, bc2);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
@@ -477,7 +479,7 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, fl
     }
   }
   for (long i = n4 * 4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-    adam_one(p[i], g[i] * gscale, m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(p[i], clip_grad(g[i], gs, cv), m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2);
     if (zero_g) g[i] = 0.f;
     if (shadow != nullptr) shadow[i] = f2bf(p[i]);
     const long e = i - t_off;
@@ -501,8 +503,10 @@ __global__ __launch_bounds__(256) void lstm_adam_pack_kernel(float* __restrict__
                                                              float* __restrict__ m, float* __restrict__ v, long n,
                                                              float* __restrict__ step, float lr, float b1, float b2,
                                                              float eps, float wd, float gscale, int zero_g, int KX, int H,
-                                                             bf16_t* __restrict__ Wp, bf16_t* __restrict__ WhhT) {
+                                                             bf16_t* __restrict__ Wp, bf16_t* __restrict__ WhhT,
+                                                             const float* __restrict__ clip, float cv) {
   const float t = step[0] + 1.f;
+  const float gs = clip_gscale(gscale, clip);
   const float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   const int KA = KX + H, G = 4 * H;
   // the W block in 32 x 32 tiles (KX, H multiples of 32, host-checked): thread = 4 consecutive
@@ -520,10 +524,10 @@ __global__ __launch_bounds__(256) void lstm_adam_pack_kernel(float* __restrict__
     float4 gg = reinterpret_cast<const float4*>(g)[i];
     float4 mm = reinterpret_cast<float4*>(m)[i];
     float4 vv = reinterpret_cast<float4*>(v)[i];
-    adam_one(pp.x, gg.x * gscale, mm.x, vv.x, lr, b1, b2, eps, wd, bc1, bc2);
-    adam_one(pp.y, gg.y * gscale, mm.y, vv.y, lr, b1, b2, eps, wd, bc1, bc2);
-    adam_one(pp.z, gg.z * gscale, mm.z, vv.z, lr, b1, b2, eps, wd, bc1, bc2);
-    adam_one(pp.w, gg.w * gscale, mm.w, vv.w, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.x, clip_grad(gg.x, gs, cv), mm.x, vv.x, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.y, clip_grad(gg.y, gs, cv), mm.y, vv.y, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.z, clip_grad(gg.z, gs, cv), mm.z, vv.z, lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(pp.w, clip_grad(gg.w, gs, cv), mm.w, vv.w, lr, b1, b2, eps, wd, bc1, bc2);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
@@ -548,7 +552,7 @@ __global__ __launch_bounds__(256) void lstm_adam_pack_kernel(float* __restrict__
   // the head (w_out, b_out) past the W block
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)G * KA + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-    adam_one(p[i], g[i] * gscale, m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2);
+    adam_one(p[i], clip_grad(g[i], gs, cv), m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2);
     if (zero_g) g[i] = 0.f;
   }
   __syncthreads();
@@ -563,24 +567,26 @@ __global__ __launch_bounds__(256) void lstm_adam_pack_kernel(float* __restrict__
 
 void launch_lstm_adam_pack(float* p, float* g, float* m, float* v, long n, float* step, float lr, float b1, float b2,
                            float eps, float wd, float gscale, int zero_g, int KX, int H, bf16_t* Wp, bf16_t* WhhT,
-                           hipStream_t s) {
+                           hipStream_t s, const float* clip, float clipvalue) {
   static const int cap = std::max(1, diag_env_int("WELLFLOW_ADAM_GRID", 256));
   int blocks = ew_blocks(n);
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(lstm_adam_pack_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step, lr, b1, b2, eps, wd,
-                     gscale, zero_g, KX, H, Wp, WhhT);
+                     gscale, zero_g, KX, H, Wp, WhhT, clip, clipvalue);
 }
 
 void launch_adam_dev(float* p, float* g, float* m, float* v, long n, float* step, float lr,
                      float b1, float b2, float eps, float wd, float gscale, bf16_t* shadow, int zero_g,
-                     hipStream_t s, bf16_t* tdst, long t_off, int t_rows, int t_cols) {
+                     hipStream_t s, bf16_t* tdst, long t_off, int t_rows, int t_cols, const float* clip,
+                     float clipvalue) {
   // every workgroup draws a ticket from ONE counter (step[1]) and same-address atomics serialise:
   // at most WELLFLOW_ADAM_GRID (default 256) workgroups, grid-stride over the rest
   static const int cap = std::max(1, diag_env_int("WELLFLOW_ADAM_GRID", 256));  // sweep: WF_DIAG builds only
   int blocks = ew_blocks(n);
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(adam_dev_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step, lr,
-                     b1, b2, eps, wd, gscale, shadow, zero_g, tdst, t_off, t_rows, t_cols);
+                     b1, b2, eps, wd, gscale, shadow, zero_g, tdst, t_off, t_rows, t_cols, clip,
+                     clipvalue);
 }
 
 // Keras-0.x SGD: v = mu v - lr_t g; p += mu v - lr_t g (Nesterov) or p += v.
@@ -612,12 +618,13 @@ void launch_sgd(float* p, const float* g, float* vel, long n, float lr, float mo
 __global__ __launch_bounds__(256) void sgd_dev_kernel(float* __restrict__ p, float* __restrict__ g,
                                                       float* __restrict__ vel, long n, float* __restrict__ step,
                                                       float lr, float decay, float momentum, int nesterov,
-                                                      float gscale, int zero_g) {
+                                                      float gscale, int zero_g, const float* __restrict__ clip, float cv) {
   const float it = step[0];
+  const float gs = clip_gscale(gscale, clip);
   const float lr_t = lr / (1.f + decay * it);
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gi = g[i] * gscale;
+    const float gi = clip_grad(g[i], gs, cv);
     const float v = momentum * vel[i] - lr_t * gi;
     vel[i] = v;
     p[i] += nesterov ? (momentum * v - lr_t * gi) : v;
@@ -634,12 +641,111 @@ __global__ __launch_bounds__(256) void sgd_dev_kernel(float* __restrict__ p, flo
 }
 
 void launch_sgd_dev(float* p, float* g, float* vel, long n, float* step, float lr, float decay, float momentum,
-                    int nesterov, float gscale, int zero_g, hipStream_t s) {
+                    int nesterov, float gscale, int zero_g, hipStream_t s, const float* clip, float clipvalue) {
   long b = (n + 255) / 256;
   if (b > 2048) b = 2048;
   if (b < 1) b = 1;
   hipLaunchKernelGGL(sgd_dev_kernel, dim3((int)b), dim3(256), 0, s, p, g, vel, n, step, lr, decay, momentum,
-                     nesterov, gscale, zero_g);
+                     nesterov, gscale, zero_g, clip, clipvalue);
+}
+
+// ---------------------------------------------------------------- gradient clipping (clipnorm)
+// Global L2 norm of the effective gradient gscale * g over the whole flat bucket, and from it the
+// factor the fused updates above multiply into their gradient scale (clip_gscale, common.h):
+// Keras 0.x clipnorm, factor = c / norm when norm >= c, else 1; a non-finite norm gives 1.
+// One launch in front of the update, nothing leaves the device, so a captured step recomputes
+// it on every replay.
+//
+// Each workgroup stores ONE partial sum of squares to partial[blockIdx.x]; the LAST workgroup to
+// arrive (ticket in state[4], which it resets: the idiom of step[1] in adam_dev_kernel) adds the
+// partials in index order and writes the state block. No float atomics, so the sum does not
+// depend on the order in which workgroups finish; no workgroup waits for another.
+// Hand-off: the partial is an agent-scope store, then __threadfence() (release) before the ticket
+// add; the last workgroup fences (acquire) after its ticket and before the barrier that lets its
+// other waves read, and reads every partial with agent-scope loads.
+//
+// state: [0] factor  [1] norm of this step  [2] steps clipped since the last reset
+//        [3] largest norm since the last reset (NaN once a norm was NaN)  [4] ticket (unsigned)
+//
+// fp32 addition chain k (tests/test_clip_gpu.py builds its tolerance from the same formula):
+//   per lane 4 accumulators (the float4 components), each `iters` additions,
+//     iters = ceil((n / 4) / (grid * 256));
+//   (x + y) + (z + w): 2;  the scalar tail element (n % 4, workgroup 0): 1;
+//   wave64 xor tree: 6;  the 4 waves of the workgroup as a tree: 2;
+//   the partials are summed in fp64 (a tree over <= 256 values): 0.
+//   k = iters + 11  (16 at the LSTM's 1.18 M floats). With the two roundings of (g * gscale)^2 per
+//   element and the fp64 sqrt rounded to fp32, the norm's relative error is below
+//   ((k + 3) / 2 + 1) * 2^-24 < k * 2^-23.
+__global__ __launch_bounds__(256) void grad_clip_scale_kernel(const float* __restrict__ g, long n, float gscale,
+                                                              float clipnorm, float* partial, float* state) {
+  __shared__ float redf[4];
+  __shared__ double redd[4];
+  __shared__ int is_last;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const long n4 = n / 4;
+  const long stride = (long)gridDim.x * blockDim.x;
+  float ax = 0.f, ay = 0.f, az = 0.f, aw = 0.f;
+  // (four loads in flight per lane instead of one changed nothing: 11.5 -> 11.7 us at the LSTM's
+  // 1.2 M floats, profiles/r7/grad_clip/README.md; the hand-off below is the cost, not this loop)
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    const float x = gg.x * gscale, y = gg.y * gscale, z = gg.z * gscale, w = gg.w * gscale;
+    ax += x * x;
+    ay += y * y;
+    az += z * z;
+    aw += w * w;
+  }
+  float s = (ax + ay) + (az + aw);
+  if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {  // the n % 4 tail
+    const float x = g[n4 * 4 + threadIdx.x] * gscale;
+    s += x * x;
+  }
+  s = wave_sum(s);
+  if (lane == 0) redf[wid] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float part = (redf[0] + redf[1]) + (redf[2] + redf[3]);
+    __hip_atomic_store(partial + blockIdx.x, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();  // release: the partial is visible device-wide before the ticket moves
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned* ticket = reinterpret_cast<unsigned*>(state + 4);
+    const bool last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+    if (last) {
+      __threadfence();  // acquire: the reads below are ordered after the ticket
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    is_last = last ? 1 : 0;
+  }
+  __syncthreads();
+  if (!is_last) return;
+  // every other workgroup has published its partial: a fixed fp64 tree over partial[0 .. grid)
+  double d = threadIdx.x < gridDim.x
+                 ? (double)__hip_atomic_load(partial + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                 : 0.0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+  if (lane == 0) redd[wid] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float nrm = (float)sqrt((redd[0] + redd[1]) + (redd[2] + redd[3]));
+    const bool finite = fabsf(nrm) <= 3.402823466e+38f;  // false for inf and NaN
+    const bool clipped = finite && clipnorm > 0.f && nrm >= clipnorm;
+    state[0] = clipped ? __fdiv_rn(clipnorm, nrm) : 1.f;
+    state[1] = nrm;
+    if (clipped) state[2] += 1.f;
+    const float mx = state[3];
+    state[3] = nrm != nrm ? nrm : fmaxf(mx, nrm);
+    __hip_atomic_store(reinterpret_cast<unsigned*>(state + 4), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+void launch_grad_clip_scale(const float* g, long n, float gscale, float clipnorm, float* partial, float* state,
+                            hipStream_t s) {
+  // every workgroup draws a ticket from ONE counter and the last one reads a partial per thread:
+  // at most kGradClipMaxBlocks (256, launch_adam_dev's cap for the same reason), grid-stride over the rest
+  int blocks = ew_blocks(n);
+  if (blocks > kGradClipMaxBlocks) blocks = kGradClipMaxBlocks;
+  hipLaunchKernelGGL(grad_clip_scale_kernel, dim3(blocks), dim3(256), 0, s, g, n, gscale, clipnorm, partial, state);
 }
 
 // ---------------------------------------------------------------- casts

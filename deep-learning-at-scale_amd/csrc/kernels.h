@@ -219,7 +219,7 @@ long cnn_part_floats(int B, const CnnDims& d, long* wd, long* wc, long* f);
 // Keras SGD over the CNN's flat parameters + the bf16 operand images of launch_cnn_pack, one launch
 void launch_cnn_sgd_pack(float* p, float* g, float* vel, long n, float* step, float lr, float decay, float momentum,
                          int nesterov, float gscale, int zero_g, const CnnDims& d, bf16_t* WcA, bf16_t* WdF,
-                         bf16_t* WdB, hipStream_t s);
+                         bf16_t* WdB, hipStream_t s, const float* clip = nullptr, float clipvalue = 0.f);
 void launch_cnn_pack(const float* Wc, const float* Wd, const CnnDims& d, bf16_t* WcA, bf16_t* WdF, bf16_t* WdB,
                      hipStream_t s);
 // train = 1: dropout + loss; dout [rows >= B rounded up to 16][16] = scale * dloss/dpred, part
@@ -256,14 +256,23 @@ void launch_adam(float* p, const float* g, float* m, float* v, long n, float lr,
 // Adam over the LSTM's flat parameters + its bf16 compute copies Wp / WhhT (lstm_pack_weights) in one launch
 void launch_lstm_adam_pack(float* p, float* g, float* m, float* v, long n, float* step, float lr, float b1, float b2,
                            float eps, float wd, float gscale, int zero_g, int KX, int H, bf16_t* Wp, bf16_t* WhhT,
-                           hipStream_t s);
+                           hipStream_t s, const float* clip = nullptr, float clipvalue = 0.f);
 void launch_adam_dev(float* p, float* g, float* m, float* v, long n, float* step, float lr,
                      float b1, float b2, float eps, float wd, float gscale, bf16_t* shadow, int zero_g,
-                     hipStream_t s, bf16_t* tdst = nullptr, long t_off = 0, int t_rows = 0, int t_cols = 0);
+                     hipStream_t s, bf16_t* tdst = nullptr, long t_off = 0, int t_rows = 0, int t_cols = 0,
+                     const float* clip = nullptr, float clipvalue = 0.f);
 void launch_sgd(float* p, const float* g, float* vel, long n, float lr, float momentum,
                 int nesterov, float gscale, hipStream_t s);
 void launch_sgd_dev(float* p, float* g, float* vel, long n, float* step, float lr, float decay, float momentum,
-                    int nesterov, float gscale, int zero_g, hipStream_t s);
+                    int nesterov, float gscale, int zero_g, hipStream_t s, const float* clip = nullptr,
+                    float clipvalue = 0.f);
+// clipnorm: the L2 norm of gscale * g[0 .. n) and the factor min(1, clipnorm / norm) into `state`
+// (kGradClipStateFloats floats: factor, norm, clipped steps, largest norm, ticket); `partial` is
+// scratch of kGradClipMaxBlocks floats. The update launchers above take `state` as their `clip`.
+constexpr int kGradClipMaxBlocks = 256;
+constexpr int kGradClipStateFloats = 8;
+void launch_grad_clip_scale(const float* g, long n, float gscale, float clipnorm, float* partial, float* state,
+                            hipStream_t s);
 void launch_cast_bf16(const float* src, bf16_t* dst, long n, hipStream_t s);
 // dst[r] = src[clamp(idx[r], 0, nsrc - 1)], rows of row_bytes (multiple of 4) bytes
 void launch_gather_rows(const void* src, const long long* idx, void* dst, long m, int row_bytes, long nsrc,

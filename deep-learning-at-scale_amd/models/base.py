@@ -78,6 +78,10 @@ def native_loss_kind(kind: str) -> int:
     return {"mse": 0, "mae_clip": 1}[kind]
 
 
+# NativeMLP / NativeCNN.small_steps_reason, checked last: the K-steps-per-launch kernels update
+# inside the launch, where the whole gradient never exists at one place, so there is no global norm
+CLIP_STEPS_REASON = "gradient clipping (clipnorm / clipvalue) needs the whole gradient: per-step update"
+
 _NOTED: set = set()
 
 

@@ -31,7 +31,7 @@ import os
 import torch
 from torch import nn
 
-from .base import note_slow_path
+from .base import CLIP_STEPS_REASON, note_slow_path
 
 
 def _r8(x: int) -> int:
@@ -292,6 +292,8 @@ class NativeCNN:
                 return "optimizer is not a device FlatSGD over this engine's parameters"
         if X is not None and not (torch.is_tensor(X) and X.dtype == torch.float32 and X.is_cuda):
             return "data not a resident fp32 tensor"
+        if opt is not None and opt.clips:
+            return CLIP_STEPS_REASON
         return None
 
     def fused_steps(self, X: torch.Tensor, Y: torch.Tensor, B: int, K: int, opt, grad_scale: float,
@@ -342,7 +344,7 @@ class NativeCNN:
             return False
         self._C.cnn_sgd_pack(self.params, self.grads, opt.vel, opt.step_dev, opt.lr, opt.decay, opt.momentum,
                              opt.nesterov, grad_scale, opt.zero_grads, self.lay.fused_dims, self.WcA, self.WdF,
-                             self.WdB)
+                             self.WdB, *opt.clip_args(grad_scale))
         return True
 
     def sync_weights(self):

@@ -282,7 +282,8 @@ class NativeLSTM:
             return False
         b1, b2 = opt.betas
         self._C.lstm_adam_pack(self.params, self.grads, opt.m, opt.v, opt.step_dev, opt.lr, b1, b2, opt.eps,
-                               opt.weight_decay, grad_scale, opt.zero_grads, self.Wp, self.WhhT, self.H, self.lay.KX)
+                               opt.weight_decay, grad_scale, opt.zero_grads, self.Wp, self.WhhT, self.H, self.lay.KX,
+                               *opt.clip_args(grad_scale))
         return True
 
     def sync_weights(self) -> None:

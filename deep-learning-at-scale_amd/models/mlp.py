@@ -25,7 +25,7 @@ import os
 import torch
 from torch import nn
 
-from .base import note_slow_path
+from .base import CLIP_STEPS_REASON, note_slow_path
 
 
 # floats of the spread-reduction scratch (csrc/kernels.h kMlpRedFloats: 64 x 9216 copies,
@@ -405,6 +405,8 @@ class NativeMLP:
                 return "optimizer is not a device FlatAdam over this engine's parameters"
         if X is not None and not (torch.is_tensor(X) and X.dtype == torch.bfloat16 and X.is_cuda):
             return "data not a resident bf16 tensor (the engine's input_dtype)"
+        if opt is not None and opt.clips:
+            return CLIP_STEPS_REASON
         return None
 
     def fused_steps(self, X: torch.Tensor, Y: torch.Tensor, B: int, K: int, opt, grad_scale: float,

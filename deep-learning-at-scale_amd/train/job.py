@@ -36,11 +36,12 @@ def _optimizer(cfg: RunConfig, eng):
     its bf16 shadow and the transposed W2 block — so no zero-fill or sync_weights launches run
     per step (without them the MLP job's step ran ~17 % slower on the device than the bench's)."""
     native = bool(getattr(eng, "native", False))
+    clip = dict(clipnorm=cfg.clipnorm, clipvalue=cfg.clipvalue)
     if cfg.optimizer == "sgd":
         return make_optimizer("sgd", eng.params, eng.grads, lr=cfg.lr, momentum=cfg.momentum,
                               decay=cfg.decay, nesterov=cfg.nesterov, zero_grads=native,
-                              writeback=eng if hasattr(eng, "fused_sgd") else None)
-    kw = {}
+                              writeback=eng if hasattr(eng, "fused_sgd") else None, **clip)
+    kw = dict(clip)
     if hasattr(eng, "fused_adam"):
         kw["writeback"] = eng
     elif native and getattr(eng, "shadow", None) is not None and hasattr(eng, "shadow_t"):

@@ -22,6 +22,7 @@ import time
 
 import torch
 
+from ..models.base import CLIP_STEPS_REASON, note_slow_path
 from .trainer import _input_format, _to_dev
 
 
@@ -186,6 +187,9 @@ def fit_online(trainer, train, val):
             and getattr(eng, "small_steps_reason", None) is not None):
         probe = torch.empty((b_full,) + tuple(Xs.shape[1:]), dtype=Xs.dtype, device=eng.device)
         why = eng.small_steps_reason(b_full, trainer.opt, probe)
+        if why == CLIP_STEPS_REASON:  # checked last: clipping alone keeps the job off the K-step launch
+            note_slow_path(type(eng).__name__, "training runs one update per step, not K steps per launch",
+                           why, f"B={b_full}")
         if why is None:
             staged = _ChunkStage(Xs, Ys, max(pr for *_, pr in plans), eng.device)
         elif cfg.verbose >= 1 and ctx.is_main:

@@ -355,6 +355,8 @@ class Trainer:
                "val_loss": h.val_loss[-1], "val_mse": h.val_mse[-1], "rows_per_s": h.rows_per_s[-1],
                "epoch_time_s": h.epoch_time[-1], "world_size": self.ctx.world_size,
                "time": time.time()}
+        if getattr(self.opt, "clips", False):  # gradient norms of this epoch's steps (optim/flat.py clip_stats)
+            rec.update(self.opt.clip_stats(reset=True))
         with open(path, "a") as f:
             f.write(json.dumps(rec) + "\n")
 
@@ -485,6 +487,14 @@ class Trainer:
         # one process (the update has no all-reduce)
         small = (getattr(eng, "small_steps_reason", None) is not None and ctx.world_size == 1 and cfg.fail_at_step < 0
                  and eng.small_steps_reason(b, self.opt, Xd) is None)
+        if (not small and getattr(self.opt, "clips", False) and ctx.world_size == 1 and cfg.fail_at_step < 0
+                and getattr(eng, "small_steps_reason", None) is not None):
+            from ..models.base import CLIP_STEPS_REASON, note_slow_path
+
+            # the reason checked last: a clipping optimizer is all that keeps this job off the K-step launch
+            if eng.small_steps_reason(b, self.opt, Xd) == CLIP_STEPS_REASON:
+                note_slow_path(type(eng).__name__, "training runs one update per step, not K steps per launch",
+                               CLIP_STEPS_REASON, f"B={b}")
         while small and s < steps:
             clock.first()
             n = min(steps - s, SMALL_STEPS_PER_LAUNCH)
