@@ -985,23 +985,29 @@ void transpose_cast_bf16(const at::Tensor& src, int64_t lds, int64_t rows, int64
 // table). cat_off / cat_size int32 [C], mean / std fp32 [Q] (device); C = 0 or Q = 0: pass None.
 constexpr int64_t kAssembleMaxF = 512;
 
-void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
-                       c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
-                       c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t N, int64_t F,
-                       const at::Tensor& out) {
+// The shared body. `Ntot`: rows of the source columns (the plain call: N, row0 = 0). With
+// perm_col in [0, C + Q) (categorical columns first) that source column is read through `perm`
+// (int32 [N], indices into all Ntot rows; the kernel clamps them).
+static void assemble_features_impl(const c10::optional<at::Tensor>& codes, const c10::optional<at::Tensor>& cont,
+                                   const c10::optional<at::Tensor>& cat_off, const c10::optional<at::Tensor>& cat_size,
+                                   const c10::optional<at::Tensor>& mean, const c10::optional<at::Tensor>& stdv,
+                                   int64_t row0, int64_t N, int64_t Ntot, int64_t F, const at::Tensor& out,
+                                   int64_t perm_col, const c10::optional<at::Tensor>& perm) {
   TORCH_CHECK(N >= 1, "assemble_features: no rows");
+  TORCH_CHECK(row0 >= 0 && row0 + N <= Ntot, "assemble_features: rows ", row0, " .. ", row0 + N, " outside the ", Ntot,
+              " source rows");
   TORCH_CHECK(F >= 1 && F <= kAssembleMaxF, "assemble_features: F = ", F, " outside 1 .. ", kAssembleMaxF);
   const bool has_c = codes.has_value() && codes->defined() && codes->numel() > 0;
   const bool has_q = cont.has_value() && cont->defined() && cont->numel() > 0;
   int64_t C = 0, Q = 0;
   if (has_c) {
     check_t(*codes, at::kInt, "codes");
-    TORCH_CHECK(codes->dim() == 2 && codes->size(1) == N, "assemble_features: codes must be [C][N]");
+    TORCH_CHECK(codes->dim() == 2 && codes->size(1) == Ntot, "assemble_features: codes must be [C][N]");
     C = codes->size(0);
   }
   if (has_q) {
     check_t(*cont, at::kFloat, "cont");
-    TORCH_CHECK(cont->dim() == 2 && cont->size(1) == N, "assemble_features: cont must be [Q][N]");
+    TORCH_CHECK(cont->dim() == 2 && cont->size(1) == Ntot, "assemble_features: cont must be [Q][N]");
     Q = cont->size(0);
   }
   TORCH_CHECK(Q <= F && C <= F, "assemble_features: more source columns than features");
@@ -1021,11 +1027,72 @@ void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(out.device());
   const int* cp = has_c ? codes->data_ptr<int>() : nullptr;
   const float* xp = has_q ? cont->data_ptr<float>() : nullptr;
+  wf::AssemblePerm pm;
+  pm.ld_src = Ntot;
+  const bool has_p = perm.has_value() && perm->defined();
+  TORCH_CHECK(has_p == (perm_col >= 0), "assemble_features: perm and perm_col go together");
+  if (has_p) {
+    TORCH_CHECK(perm_col < C + Q, "assemble_features: perm_col ", perm_col, " outside 0 .. ", C + Q - 1);
+    TORCH_CHECK(perm->is_cuda() && perm->scalar_type() == at::kInt && perm->is_contiguous() && perm->dim() == 1,
+                "assemble_features: perm must be a contiguous int32 GPU vector");
+    TORCH_CHECK(perm->numel() == N, "assemble_features: perm holds ", perm->numel(), " indices for ", N, " rows");
+    TORCH_CHECK(Ntot <= INT32_MAX, "assemble_features: int32 perm cannot index ", Ntot, " rows");
+    pm.src = (int)perm_col;
+    pm.perm = perm->data_ptr<int>();
+    pm.base = perm_col < C ? static_cast<const void*>(cp + perm_col * Ntot)
+                           : static_cast<const void*>(xp + (perm_col - C) * Ntot);
+    pm.n = Ntot;
+  }
+  if (cp != nullptr) cp += row0;
+  if (xp != nullptr) xp += row0;
   const bool ok = bf ? wf::launch_assemble_features_bf16(cp, xp, off, size, mu, sd, N, (int)C, (int)Q, (int)F, (int)ld,
-                                                         bfp(out), cur_stream())
+                                                         bfp(out), cur_stream(), pm)
                      : wf::launch_assemble_features_f32(cp, xp, off, size, mu, sd, N, (int)C, (int)Q, (int)F, (int)ld,
-                                                        fp(out), cur_stream());
+                                                        fp(out), cur_stream(), pm);
   TORCH_CHECK(ok, "assemble_features: the launcher refused the shape");
+}
+
+void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
+                       c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
+                       c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t N, int64_t F,
+                       const at::Tensor& out) {
+  assemble_features_impl(codes, cont, cat_off, cat_size, mean, stdv, 0, N, N, F, out, -1, c10::nullopt);
+}
+
+// Rows [row0, row0 + N) of resident source columns ([C][Ntot] / [Q][Ntot], read in place), with
+// source column perm_col (or -1) read through perm: the permutation-importance pass.
+void assemble_features_rows(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
+                            c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
+                            c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t row0, int64_t N,
+                            int64_t F, const at::Tensor& out, int64_t perm_col, c10::optional<at::Tensor> perm) {
+  int64_t Ntot = -1;
+  if (codes.has_value() && codes->defined() && codes->numel() > 0 && codes->dim() == 2) Ntot = codes->size(1);
+  else if (cont.has_value() && cont->defined() && cont->numel() > 0 && cont->dim() == 2) Ntot = cont->size(1);
+  TORCH_CHECK(Ntot >= 1, "assemble_features: no source columns");
+  assemble_features_impl(codes, cont, cat_off, cat_size, mean, stdv, row0, N, Ntot, F, out, perm_col, perm);
+}
+
+// Scoring-error sums (score.hip): out[slot] = {sum d^2, sum |d|}, d = pred * y_scale + y_shift - y
+// in fp64. pred / y fp32 [M] (views of larger vectors allowed), out fp64 [S][2], scratch fp64
+// [kErrSumsScratch] zeroed once by the caller. Stream-ordered; nothing is read back here.
+void err_sums(const at::Tensor& pred, const at::Tensor& y, double y_scale, double y_shift, const at::Tensor& out,
+              int64_t slot, const at::Tensor& scratch) {
+  for (const at::Tensor* t : {&pred, &y}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 1,
+                "err_sums: pred / y must be contiguous fp32 GPU vectors");
+  }
+  TORCH_CHECK(pred.numel() >= 1 && pred.numel() == y.numel(), "err_sums: pred holds ", pred.numel(), " elements, y ",
+              y.numel(), " (need the same, >= 1)");
+  check_t(out, at::kDouble, "out");
+  check_t(scratch, at::kDouble, "scratch");
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == 2, "err_sums: out must be fp64 [S][2]");
+  TORCH_CHECK(slot >= 0 && slot < out.size(0), "err_sums: slot ", slot, " outside 0 .. ", out.size(0) - 1);
+  check_extent(scratch, wf::kErrSumsScratch, "scratch");
+  TORCH_CHECK(pred.device() == y.device() && pred.device() == out.device() && pred.device() == scratch.device(),
+              "err_sums: tensors on different devices");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(pred.device());
+  wf::launch_err_sums(pred.data_ptr<float>(), y.data_ptr<float>(), pred.numel(), y_scale, y_shift,
+                      out.data_ptr<double>() + 2 * slot, scratch.data_ptr<double>(), cur_stream());
 }
 
 void im2col1d(const at::Tensor& x, int64_t B, int64_t L, int64_t Cin, int64_t ksz, int64_t Kp,
@@ -1313,7 +1380,7 @@ struct Checked<F> {
 }  // namespace
 
 #define WF_DEF(name) m.def(#name, &Checked<&name>::call)
-// a second overload of `name`: the call shape from before the trailing clip arguments
+// a second overload of `name` (e.g. the call shape from before the trailing clip arguments)
 #define WF_DEF_AS(name, fn) m.def(#name, &Checked<&fn>::call)
 
 PYBIND11_MODULE(_C, m) {
@@ -1355,6 +1422,8 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(transpose_cast_bf16);
   WF_DEF(im2col1d);
   WF_DEF(assemble_features);
+  WF_DEF_AS(assemble_features, assemble_features_rows);  // + row range and one permuted source column
+  WF_DEF(err_sums);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
   m.def("cnn_fused_ok", &cnn_fused_ok);

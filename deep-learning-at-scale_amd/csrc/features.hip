@@ -29,6 +29,18 @@
 //      lane's dwords, against 4 in the unrotated order.
 // No atomics; plain vector stores; any N >= 1 (the tail tile copies rows x D dwords, the last
 // < 4 of them as single dwords); C = 0 or Q = 0 allowed; grid-stride over tiles.
+//
+// Source columns are ld_src elements apart (>= N): a piece of a larger resident table is
+// assembled by pointing codes / cont at its first row, without a copy of the piece.
+//
+// One permuted source (permutation importance, wellflow/importance.py). With perm_src in
+// [0, C + Q) (the kernel's source order: categorical columns, then continuous) output row r takes
+// THAT column's value from perm_base[clamp(perm[r], 0, perm_n - 1)]: perm_base / perm_n are the
+// base and length of the whole source column, so a piece gathers from all rows of the table. The
+// clamp is unconditional (gather_rows_kernel, elementwise.hip): a bad index is never an
+// out-of-bounds read. The wave index is the source column, so the branch is wave-uniform: one
+// wave per tile gathers (64 4-B reads, a 32-B sector each), every other column is read as
+// before, coalesced and once. perm_src = -1: no column matches, the launch is the plain one.
 #include "common.h"
 #include "kernels.h"
 
@@ -56,7 +68,8 @@ template <typename OutT>
 __global__ __launch_bounds__(kAsmThreads) void assemble_features_kernel(
     const int* __restrict__ codes, const float* __restrict__ cont, const int* __restrict__ cat_off,
     const int* __restrict__ cat_size, const float* __restrict__ mean, const float* __restrict__ stdv, long N, int C,
-    int Q, int F, int ld, OutT* __restrict__ out) {
+    int Q, int F, int ld, OutT* __restrict__ out, long ld_src, int perm_src, const int* __restrict__ perm,
+    const void* __restrict__ perm_base, long perm_n) {
   extern __shared__ unsigned asm_tile[];  // [kAsmRows][Dp] dwords
   constexpr int EPD = 4 / (int)sizeof(OutT);  // elements per dword
   const int D = ld / EPD;                     // dwords per output row (bf16: ld % 8 == 0)
@@ -74,14 +87,21 @@ __global__ __launch_bounds__(kAsmThreads) void assemble_features_kernel(
     if (lane < rows) {
       OutT* const trow = telem + (long)lane * Dp * EPD;
       for (int s = wave; s < C + Q; s += kAsmThreads / 64) {
+        const bool permuted = s == perm_src;  // wave-uniform
+        long pr = 0;
+        if (permuted) {
+          pr = perm[row0 + lane];
+          pr = pr < 0 ? 0 : (pr >= perm_n ? perm_n - 1 : pr);
+        }
         if (s < C) {
-          const int code = codes[(long)s * N + row0 + lane];
+          const int code = permuted ? static_cast<const int*>(perm_base)[pr] : codes[(long)s * ld_src + row0 + lane];
           const int col = cat_off[s] + code;
           // col < Fc also when the block spec itself were wrong: never a write outside the row
           if ((unsigned)code < (unsigned)cat_size[s] && (unsigned)col < (unsigned)Fc) trow[col] = AsmOut<OutT>::cvt(1.0f);
         } else {
           const int q = s - C;
-          trow[Fc + q] = AsmOut<OutT>::cvt((cont[(long)q * N + row0 + lane] - mean[q]) / stdv[q]);
+          const float x = permuted ? static_cast<const float*>(perm_base)[pr] : cont[(long)q * ld_src + row0 + lane];
+          trow[Fc + q] = AsmOut<OutT>::cvt((x - mean[q]) / stdv[q]);
         }
       }
     }
@@ -127,7 +147,10 @@ size_t assemble_features_lds_bytes(int ld, bool bf16_out) {
 template <typename OutT>
 static bool launch_assemble(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                             const float* mean, const float* stdv, long N, int C, int Q, int F, int ld, OutT* out,
-                            hipStream_t s) {
+                            hipStream_t s, const AssemblePerm& pm) {
+  // a permuted source needs its index vector and a non-empty column to clamp into
+  if (pm.src >= 0 && (pm.src >= C + Q || pm.perm == nullptr || pm.base == nullptr || pm.n < 1)) return false;
+  if (pm.ld_src != 0 && pm.ld_src < N) return false;
   const size_t lds = assemble_features_lds_bytes(ld, sizeof(OutT) == 2);
   if (lds > kAssembleMaxLds) return false;
   auto kern = assemble_features_kernel<OutT>;
@@ -139,20 +162,20 @@ static bool launch_assemble(const int* codes, const float* cont, const int* cat_
   // capped grid: 8 workgroups per CU of a 256-CU device keep ~0.5 MB of column reads in flight
   const long grid = ntiles < 2048 ? ntiles : 2048;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kAsmThreads), lds, s, codes, cont, cat_off, cat_size, mean, stdv,
-                     N, C, Q, F, ld, out);
+                     N, C, Q, F, ld, out, pm.ld_src ? pm.ld_src : N, pm.src >= 0 ? pm.src : -1, pm.perm, pm.base, pm.n);
   return true;
 }
 
 bool launch_assemble_features_bf16(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                                    const float* mean, const float* stdv, long N, int C, int Q, int F, int ld,
-                                   bf16_t* out, hipStream_t s) {
-  return launch_assemble<bf16_t>(codes, cont, cat_off, cat_size, mean, stdv, N, C, Q, F, ld, out, s);
+                                   bf16_t* out, hipStream_t s, const AssemblePerm& pm) {
+  return launch_assemble<bf16_t>(codes, cont, cat_off, cat_size, mean, stdv, N, C, Q, F, ld, out, s, pm);
 }
 
 bool launch_assemble_features_f32(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                                   const float* mean, const float* stdv, long N, int C, int Q, int F, int ld, float* out,
-                                  hipStream_t s) {
-  return launch_assemble<float>(codes, cont, cat_off, cat_size, mean, stdv, N, C, Q, F, ld, out, s);
+                                  hipStream_t s, const AssemblePerm& pm) {
+  return launch_assemble<float>(codes, cont, cat_off, cat_size, mean, stdv, N, C, Q, F, ld, out, s, pm);
 }
 
 }  // namespace wf

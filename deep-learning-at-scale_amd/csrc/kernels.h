@@ -289,11 +289,31 @@ void launch_im2col1d(const float* x, int B, int L, int Cin, int ksz, int Lout, i
 // LDS tile is 64 x (dwords per row | 1) x 4 bytes; false = it would not fit (not launched).
 constexpr size_t kAssembleMaxLds = 160 * 1024;
 size_t assemble_features_lds_bytes(int ld, bool bf16_out);
+// Optional: source columns ld_src elements apart (0 = N: codes / cont point at the first row of a
+// piece of a larger table), and ONE source column src in [0, C + Q) (categorical first) read
+// through a row permutation: output row r takes base[clamp(perm[r], 0, n - 1)], base / n the
+// whole source column (int32 codes or fp32 values). src = -1: none.
+struct AssemblePerm {
+  long ld_src = 0;
+  int src = -1;
+  const int* perm = nullptr;
+  const void* base = nullptr;
+  long n = 0;
+};
 bool launch_assemble_features_bf16(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                                    const float* mean, const float* stdv, long N, int C, int Q, int F, int ld,
-                                   bf16_t* out, hipStream_t s);
+                                   bf16_t* out, hipStream_t s, const AssemblePerm& pm = AssemblePerm());
 bool launch_assemble_features_f32(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                                   const float* mean, const float* stdv, long N, int C, int Q, int F, int ld, float* out,
-                                  hipStream_t s);
+                                  hipStream_t s, const AssemblePerm& pm = AssemblePerm());
+
+// ---- scoring-error reduction (score.hip) ----
+// d = (double)pred * y_scale + y_shift - (double)y over M >= 1 elements; out2 = {sum d^2, sum |d|},
+// fp64 throughout, bitwise repeatable for a given M. `scratch`: kErrSumsScratch doubles (one
+// partial pair per workgroup + the ticket), zero before the first launch; left ready for the next.
+constexpr int kErrSumsMaxBlocks = 256;
+constexpr int kErrSumsScratch = 2 * kErrSumsMaxBlocks + 1;
+void launch_err_sums(const float* pred, const float* y, long M, double y_scale, double y_shift, double* out2,
+                     double* scratch, hipStream_t s);
 
 }  // namespace wf

@@ -83,6 +83,108 @@ def assemble_features(codes, cont, cat_off, cat_size, mean, std, n_features: int
     return out
 
 
+class ResidentColumns:
+    """A table's raw columns and its pipeline's block spec, uploaded ONCE: what the passes of a
+    permutation-importance run (wellflow/importance.py) assemble from, over and over, without a
+    further host check or H2D copy. The spec is checked here, on the host, as
+    :func:`assemble_features` checks it."""
+
+    def __init__(self, codes, cont, cat_off, cat_size, mean, std, n_features: int, device):
+        import numpy as np
+        import torch
+
+        self.device = dev = torch.device(device)
+        self.F = F = int(n_features)
+        off = np.asarray(cat_off, dtype=np.int64).reshape(-1)
+        size = np.asarray(cat_size, dtype=np.int64).reshape(-1)
+        codes, cont = torch.as_tensor(codes), torch.as_tensor(cont)
+        self.C = C = codes.shape[0] if codes.numel() else 0
+        self.Q = Q = cont.shape[0] if cont.numel() else 0
+        self.N = codes.shape[1] if C else (cont.shape[1] if Q else 0)
+        if len(off) != C or len(size) != C:
+            raise ValueError(f"assemble_features: {C} code columns but {len(off)} offsets / {len(size)} sizes")
+        if C and ((size < 0).any() or (off != np.cumsum(size) - size).any()):
+            raise ValueError("assemble_features: one-hot blocks must be back to back from column 0")
+        if int(size.sum()) + Q != F:
+            raise ValueError(f"assemble_features: one-hot width {int(size.sum())} + {Q} continuous != F = {F}")
+        if Q and (cont.shape[1] != self.N or len(mean) != Q or len(std) != Q):
+            raise ValueError("assemble_features: cont / mean / std shapes disagree")
+        if self.N < 1:
+            raise ValueError("assemble_features: no rows")
+        if self.N >= 2 ** 31:
+            raise ValueError(f"assemble_features: an int32 permutation cannot index {self.N} rows")
+        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+        f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+        self.codes = codes.to(dev, torch.int32).contiguous() if C else None
+        self.cont = cont.to(dev, torch.float32).contiguous() if Q else None
+        self.off, self.size = (i32(off), i32(size)) if C else (None, None)
+        self.mean, self.std = (f32(mean), f32(std)) if Q else (None, None)
+
+    def out_width(self, out_dtype) -> int:
+        import torch
+
+        return (self.F + 7) // 8 * 8 if out_dtype == torch.bfloat16 else self.F
+
+    def assemble(self, out_dtype, rows=None, perm=None, perm_col: int = -1, out=None):
+        """Feature rows ``rows = (a, b)`` (default: all) of the resident table, as
+        :func:`assemble_features` builds them. With ``perm`` (int32 device vector of ``b - a``
+        indices into ALL N rows) source column ``perm_col`` — in the kernel's source order, the C
+        categorical columns first, then the Q continuous ones — is read through it: output row r
+        takes that column's value of row ``perm[r]`` (the kernel clamps the index into the
+        column). Everything is refused here, on the host, before a launch; nothing is uploaded."""
+        import torch
+
+        a, b = (0, self.N) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= a < b <= self.N:
+            raise ValueError(f"assemble_features: rows [{a}, {b}) outside the table's {self.N} rows")
+        perm_col = int(perm_col)
+        if (perm is None) != (perm_col < 0):
+            raise ValueError("assemble_features: perm and perm_col go together")
+        if perm is not None:
+            if not 0 <= perm_col < self.C + self.Q:
+                raise ValueError(f"assemble_features: perm_col {perm_col} outside [0, {self.C + self.Q})")
+            if not isinstance(perm, torch.Tensor) or perm.device != self.device:
+                raise ValueError(f"assemble_features: perm must be a tensor on {self.device}")
+            if perm.dtype != torch.int32:
+                raise TypeError(f"assemble_features: perm must be int32, got {perm.dtype}")
+            if perm.dim() != 1 or perm.numel() != b - a or not perm.is_contiguous():
+                raise ValueError(f"assemble_features: perm holds {tuple(perm.shape)} indices for {b - a} rows")
+        ld = self.out_width(out_dtype)
+        if out is None:
+            out = torch.empty((b - a, ld), dtype=out_dtype, device=self.device)
+        elif out.shape != (b - a, ld) or out.dtype != out_dtype or out.device != self.device:
+            raise ValueError(f"assemble_features: out must be {out_dtype} [{b - a}][{ld}] on {self.device}")
+        lib().assemble_features(self.codes, self.cont, self.off, self.size, self.mean, self.std, a, b - a, self.F, out,
+                                perm_col if perm is not None else -1, perm)
+        return out
+
+
+def err_sums(pred, y, y_scale: float, y_shift: float, out, slot: int, scratch):
+    """``out[slot] = {sum d^2, sum |d|}``, ``d = pred * y_scale + y_shift - y`` in fp64
+    (csrc/score.hip): fp32 device vectors ``pred`` / ``y`` of one length, ``out`` fp64 [S][2],
+    ``scratch`` from :func:`err_sums_scratch`. Stream-ordered; nothing comes back to the host."""
+    import torch
+
+    if pred.dtype != torch.float32 or y.dtype != torch.float32:
+        raise TypeError(f"err_sums: pred / y must be float32, got {pred.dtype} / {y.dtype}")
+    if pred.dim() != 1 or pred.shape != y.shape or pred.numel() < 1:
+        raise ValueError(f"err_sums: pred {tuple(pred.shape)} and y {tuple(y.shape)} must be equal, non-empty vectors")
+    if out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != 2 or not 0 <= int(slot) < out.shape[0]:
+        raise ValueError(f"err_sums: out must be float64 [S][2] with slot {slot} inside it")
+    lib().err_sums(pred, y, float(y_scale), float(y_shift), out, int(slot), scratch)
+
+
+ERR_SUMS_SCRATCH = 2 * 256 + 1  # csrc/kernels.h kErrSumsScratch: a partial pair per workgroup + the ticket
+
+
+def err_sums_scratch(device):
+    """The zeroed scratch block of :func:`err_sums` (one per stream; the kernel leaves it ready
+    for its next launch)."""
+    import torch
+
+    return torch.zeros(ERR_SUMS_SCRATCH, dtype=torch.float64, device=device)
+
+
 def gemm(A, B, M, N, K, *, a_mn=False, lda=None, b_mn=False, ldb=None, outF=None, outH=None,
          ldo=None, bias=None, mask=None, ldm=None, mask_scale=1.0, colsum=None, alpha=1.0,
          beta=0.0, act=0, atomic=False, ksplit=1, drop_p=0.0, seed=0, tile=0, seed_dev=None):

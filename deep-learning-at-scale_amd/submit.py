@@ -5,6 +5,9 @@ scripts under "Artificial intelligence models/" and "Physical model/").
 
 ``python -m wellflow.submit predict <model> columnNames columnTypes targetColumn storagePath dataPath``
 scores a CSV with the ``.mdl`` a training job saved (wellflow/predict.py).
+
+``python -m wellflow.submit importance <model> columnNames columnTypes targetColumn storagePath dataPath``
+ranks the input columns of that ``.mdl`` by permutation importance (wellflow/importance.py).
 """
 import sys
 
@@ -20,6 +23,10 @@ def main(argv=None) -> int:
         from .predict import main as predict_main
 
         return predict_main(argv[1:])
+    if argv[0] == "importance":  # permutation importance of a saved .mdl's input columns
+        from .importance import main as importance_main
+
+        return importance_main(argv[1:])
     run_job(argv[0], argv[1:])
     return 0
 

@@ -1,0 +1,232 @@
+#!/usr/bin/env python
+"""Permutation-importance throughput: passes/s of the device pass loop (wellflow/importance.py)
+against what a user could do before it — permute the column on the host and call
+``Predictor.predict_table`` once per pass, then take the error in numpy — on the same commit.
+
+One process, interleaved timing windows (device / host / device / host ...), so both variants see
+the same machine state. Two shapes:
+
+* MLP 16-256-256-1 on an in-memory synthetic table of N = 2,097,152 rows (6 wells: 6 + 3 one-hot
+  columns + 7 continuous);
+* LSTM (H = 512, T = 64) at its full-grid batch, 8 full chunks of windows.
+
+A device window is ``--passes`` passes of the pass loop with ONE synchronisation at its end (the
+job's shape: the host reads the sums once); a host window is ``--host-passes`` passes of host
+permute + ``predict_table`` + numpy error. The terms of a device pass (randperm, permuted
+assembly, forward(s), reduction) are also timed alone with device events, 10 launches per window.
+
+    python tools/importance_throughput.py [--rows N] [--rounds R] [--json PATH]
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o run -- \\
+        python tools/importance_throughput.py --profile-run       # the kernels' own times
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from wellflow.data.features import FeaturePipeline, take  # noqa: E402
+from wellflow.data.io import load_table  # noqa: E402
+from wellflow.data.schema import parse_schema  # noqa: E402
+from wellflow.importance import _LstmScorer, _MlpScorer  # noqa: E402
+from wellflow.models import registry  # noqa: E402
+from wellflow.predict import Predictor  # noqa: E402
+from wellflow.utils.checkpoint import save_mdl  # noqa: E402
+
+NAMES = "well,field,t,whp,choke,glr,temp,water_cut,dsp,flow"
+TYPES = "string,string,int,float,float,float,float,float,float,float"
+
+
+def _clock(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def _median(v):
+    return float(np.median(np.asarray(v, np.float64)))
+
+
+def _events(fn, launches=10):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(launches):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / launches * 1e-3
+
+
+def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
+    p = os.path.join(tmp, "models", f"{name}.mdl")
+    extra = {"features": pipe.state()}
+    if job:
+        extra["job"] = job
+    save_mdl(p, name, registry.keras_layers(name, ref), extra)
+    return Predictor.load(p, schema, device="cuda", precision="bf16", batch=batch)
+
+
+def _measure(pred, table, scorer, cols, passes, host_passes, rounds):
+    """Interleaved device / host windows over the columns ``cols`` (source indices), round robin."""
+    n = scorer.n
+    dev = pred.device
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    rng = np.random.default_rng(0)
+    y = np.asarray(table["flow"], np.float64)
+    names = scorer.names
+    scorer.begin(1 + passes)
+
+    def device_window():
+        with torch.no_grad():
+            for i in range(passes):
+                perm = torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)
+                scorer.score(1 + i, cols[i % len(cols)], perm)
+        return scorer.finish()  # the one read of the sums
+
+    def host_window():
+        out = []
+        for i in range(host_passes):
+            c = names[cols[i % len(cols)]]
+            t2 = dict(table)
+            t2[c] = np.asarray(table[c])[rng.permutation(n)]
+            p = np.asarray(pred.predict_table(t2), np.float64)
+            ok = ~np.isnan(p)
+            d = p[ok] - y[ok]
+            out.append(float(np.mean(d * d)))
+        return out
+
+    with torch.no_grad():
+        scorer.score(0, -1, None)
+    device_window()  # warm-up of both paths
+    host_window()
+    td, th = [], []
+    for _ in range(rounds):
+        td.append(_clock(device_window)[0] / passes)
+        th.append(_clock(host_window)[0] / host_passes)
+    sums = scorer.finish()
+    # the terms of one device pass, each alone
+    perm = torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)
+    k = cols[0]
+    terms = {"randperm_us": [], "assemble_us": [], "forward_us": [], "reduce_us": []}
+    with torch.no_grad():
+        for _ in range(max(rounds, 3)):
+            terms["randperm_us"].append(_events(lambda: torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)))
+            terms["assemble_us"].append(_events(lambda: scorer.assemble_only(k, perm)))
+            terms["forward_us"].append(_events(scorer.forward_only))
+            terms["reduce_us"].append(_events(lambda: scorer._reduce(0)))
+    rec = {"device": {"pass_s": _median(td), "passes_per_s": 1.0 / _median(td), "all_pass_s": td, "passes_per_window": passes},
+           "host": {"pass_s": _median(th), "passes_per_s": 1.0 / _median(th), "all_pass_s": th,
+                    "passes_per_window": host_passes},
+           "terms": {k2: _median(v) * 1e6 for k2, v in terms.items()},
+           "finite": bool(np.isfinite(sums).all())}
+    rec["speedup"] = rec["host"]["pass_s"] / rec["device"]["pass_s"]
+    return rec
+
+
+class _TimedMlp(_MlpScorer):
+    def assemble_only(self, k, perm):
+        for a in range(0, self.n, self.piece):
+            b = min(self.n, a + self.piece)
+            self.res.assemble(torch.bfloat16, rows=(a, b), perm=perm[a:b], perm_col=k, out=self.X[: b - a])
+
+    def forward_only(self):  # the table of the last assembly (one piece at these sizes)
+        m = self.X.shape[0]
+        for c in range(0, m, self.B):
+            self.p[c : min(c + self.B, m)].copy_(self.eng.forward(self.X[c : c + self.B]))
+
+
+class _TimedLstm(_LstmScorer):
+    def assemble_only(self, k, perm):
+        self.res.assemble(torch.float32, perm=perm, perm_col=k, out=self.rows)
+
+    def forward_only(self):
+        for a, m, ids in self.chunks:
+            self.p[a : a + m].copy_(self.eng.forward_windows(self.win, ids)[:m])
+
+
+def bench_mlp(rows, passes, host_passes, rounds, tmp):
+    from wellflow.models.mlp import MLPRegressor
+
+    schema = parse_schema(NAMES, TYPES)
+    wells = 6  # 6 well + 3 field one-hot columns + 7 continuous = 16 features
+    table = load_table("synth", schema, synth_wells=wells, synth_steps=(rows + wells - 1) // wells, seed=1)
+    table = take(table, np.arange(rows))  # the last well is a few rows short; every well is still there
+    n = len(table["flow"])
+    pipe = FeaturePipeline(schema, "flow", standardize_target=True).fit(take(table, np.arange(0, n, 32)))
+    torch.manual_seed(0)
+    pred = _predictor(tmp, "mlp", MLPRegressor(pipe.n_features, (256, 256)), pipe, schema)
+    t_setup, scorer = _clock(lambda: _TimedMlp(pred, table, np.asarray(table["flow"], np.float64), n, 0))
+    C, Q = scorer.res.C, scorer.res.Q
+    rec = _measure(pred, table, scorer, list(range(C + Q)), passes, host_passes, rounds)
+    rec.update(rows=n, features=pipe.n_features, engine_batch=pred.eng_batch, setup_s=t_setup,
+               pieces=(n + scorer.piece - 1) // scorer.piece)
+    return rec
+
+
+def bench_lstm(passes, host_passes, rounds, tmp):
+    from wellflow.models.lstm import LSTMRegressor, NativeLSTM
+
+    H, T, wells = 512, 64, 8
+    dev = torch.device("cuda", 0)
+    B = NativeLSTM.full_grid_batch(H, dev)
+    schema = parse_schema(NAMES, TYPES)
+    table = load_table("synth", schema, synth_wells=wells, synth_steps=T - 1 + B, seed=2)  # 8 full chunks
+    n = len(table["flow"])
+    pipe = FeaturePipeline(schema, "flow", standardize_target=True).fit(take(table, np.arange(0, n, 8)))
+    torch.manual_seed(0)
+    pred = _predictor(tmp, "lstm", LSTMRegressor(pipe.n_features, H), pipe, schema,
+                      job={"seq_len": T, "group_col": "well", "hidden": H, "mlp_hidden": [256, 256]}, batch=B)
+    t_setup, scorer = _clock(lambda: _TimedLstm(pred, table, np.asarray(table["flow"], np.float64), n))
+    C, Q = scorer.res.C, scorer.res.Q
+    rec = _measure(pred, table, scorer, list(range(C + Q)), passes, host_passes, rounds)
+    pred.eng.check_device_errors()
+    rec.update(rows=n, windows=int(scorer.M), features=pipe.n_features, engine_batch=B, setup_s=t_setup)
+    return rec
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rows", type=int, default=2_097_152)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--passes", type=int, default=18, help="device passes per timing window")
+    ap.add_argument("--host-passes", type=int, default=2, help="host passes per timing window")
+    ap.add_argument("--json", default="")
+    ap.add_argument("--skip-lstm", action="store_true")
+    ap.add_argument("--profile-run", action="store_true",
+                    help="one short round of each shape (for a kernel trace): no rates are worth reading")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        print("importance_throughput: needs a GPU (no rate is reported without one)", file=sys.stderr)
+        return 2
+    if args.profile_run:
+        args.rounds, args.host_passes = 1, 1
+    rec = {"device": torch.cuda.get_device_name(0)}
+    with tempfile.TemporaryDirectory() as tmp:
+        rec["mlp"] = bench_mlp(args.rows, args.passes, args.host_passes, args.rounds, tmp)
+        if not args.skip_lstm:
+            rec["lstm"] = bench_lstm(args.passes, args.host_passes, args.rounds, tmp)
+    line = json.dumps(rec)
+    print(line)
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
