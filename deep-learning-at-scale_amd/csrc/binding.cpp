@@ -407,7 +407,7 @@ bool lstm_backward_dw(const at::Tensor& WhhT, const at::Tensor& XH, const at::Te
 }
 
 // The clipnorm state block of grad_clip_scale (csrc/elementwise.hip) as the fused updates take it;
-// none = no clipnorm. Every update binding has its earlier call shape as a second overload.
+// none = no clipnorm.
 const float* clip_state(const c10::optional<at::Tensor>& clip) {
   return opt_ptr<float>(clip, at::kFloat, "clip", wf::kGradClipStateFloats);
 }
@@ -434,12 +434,6 @@ void lstm_adam_pack(const at::Tensor& p, const at::Tensor& g, const at::Tensor& 
   wf::launch_lstm_adam_pack(fp(p), fp(g), fp(m), fp(v), n, fp(step), (float)lr, (float)b1, (float)b2, (float)eps,
                             (float)wd, (float)gscale, zero_g ? 1 : 0, (int)KX, (int)H, bfp(Wp), bfp(WhhT), cur_stream(),
                             clip_state(clip), (float)clipvalue);
-}
-void lstm_adam_pack_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
-                           const at::Tensor& step, double lr, double b1, double b2, double eps, double wd,
-                           double gscale, bool zero_g, const at::Tensor& Wp, const at::Tensor& WhhT, int64_t H,
-                           int64_t KX) {
-  lstm_adam_pack(p, g, m, v, step, lr, b1, b2, eps, wd, gscale, zero_g, Wp, WhhT, H, KX, c10::nullopt, 0.0);
 }
 
 void lstm_pack_weights(const at::Tensor& W, const at::Tensor& Wp, const at::Tensor& WhhT,
@@ -891,13 +885,6 @@ void adam_dev(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, con
                       zero_g ? 1 : 0, cur_stream(), tdst, (long)t_off, (int)t_rows, (int)t_cols, clip_state(clip),
                       (float)clipvalue);
 }
-void adam_dev_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
-                     const at::Tensor& step, double lr, double b1, double b2, double eps, double wd, double gscale,
-                     c10::optional<at::Tensor> shadow, bool zero_g, c10::optional<at::Tensor> shadow_t, int64_t t_off,
-                     int64_t t_rows, int64_t t_cols) {
-  adam_dev(p, g, m, v, step, lr, b1, b2, eps, wd, gscale, shadow, zero_g, shadow_t, t_off, t_rows, t_cols,
-           c10::nullopt, 0.0);
-}
 
 void sgd(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, double lr,
          double momentum, bool nesterov, double gscale) {
@@ -924,10 +911,6 @@ void sgd_dev(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, co
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
   wf::launch_sgd_dev(fp(p), fp(g), fp(vel), n, fp(step), (float)lr, (float)decay, (float)momentum, nesterov ? 1 : 0,
                      (float)gscale, zero_g ? 1 : 0, cur_stream(), clip_state(clip), (float)clipvalue);
-}
-void sgd_dev_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, const at::Tensor& step, double lr,
-                    double decay, double momentum, bool nesterov, double gscale, bool zero_g) {
-  sgd_dev(p, g, vel, step, lr, decay, momentum, nesterov, gscale, zero_g, c10::nullopt, 0.0);
 }
 
 // clipnorm: norm of gscale * g and the factor min(1, clipnorm / norm) into `state` (device only)
@@ -980,25 +963,28 @@ void transpose_cast_bf16(const at::Tensor& src, int64_t lds, int64_t rows, int64
                                  cur_stream());
 }
 
-// Feature assembly on the device (features.hip): codes int32 [C][N] + cont fp32 [Q][N] ->
-// out [N][ld], bf16 (ld = round_up(F, 8), the MLP input format) or fp32 (ld = F, the LSTM row
-// table). cat_off / cat_size int32 [C], mean / std fp32 [Q] (device); C = 0 or Q = 0: pass None.
+// Feature assembly on the device (features.hip): rows [row0, row0 + N) of the source columns codes
+// int32 [C][Ntot] + cont fp32 [Q][Ntot] (read in place) -> out [N][ld], bf16 (ld = round_up(F, 8),
+// the MLP input format) or fp32 (ld = F, the LSTM row table). cat_off / cat_size int32 [C], mean /
+// std fp32 [Q] (device); C = 0 or Q = 0: pass None. With perm_col in [0, C + Q) (categorical columns
+// first; else -1 and perm None) that source column is read through `perm` (int32 [N], indices into
+// all Ntot rows; the kernel clamps them): the permutation-importance pass.
 constexpr int64_t kAssembleMaxF = 512;
 
-// The shared body. `Ntot`: rows of the source columns (the plain call: N, row0 = 0). With
-// perm_col in [0, C + Q) (categorical columns first) that source column is read through `perm`
-// (int32 [N], indices into all Ntot rows; the kernel clamps them).
-static void assemble_features_impl(const c10::optional<at::Tensor>& codes, const c10::optional<at::Tensor>& cont,
-                                   const c10::optional<at::Tensor>& cat_off, const c10::optional<at::Tensor>& cat_size,
-                                   const c10::optional<at::Tensor>& mean, const c10::optional<at::Tensor>& stdv,
-                                   int64_t row0, int64_t N, int64_t Ntot, int64_t F, const at::Tensor& out,
-                                   int64_t perm_col, const c10::optional<at::Tensor>& perm) {
+void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
+                       c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
+                       c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t row0, int64_t N,
+                       int64_t F, const at::Tensor& out, int64_t perm_col, c10::optional<at::Tensor> perm) {
+  const bool has_c = codes.has_value() && codes->defined() && codes->numel() > 0;
+  const bool has_q = cont.has_value() && cont->defined() && cont->numel() > 0;
+  int64_t Ntot = -1;
+  if (has_c && codes->dim() == 2) Ntot = codes->size(1);
+  else if (has_q && cont->dim() == 2) Ntot = cont->size(1);
+  TORCH_CHECK(Ntot >= 1, "assemble_features: no source columns");
   TORCH_CHECK(N >= 1, "assemble_features: no rows");
   TORCH_CHECK(row0 >= 0 && row0 + N <= Ntot, "assemble_features: rows ", row0, " .. ", row0 + N, " outside the ", Ntot,
               " source rows");
   TORCH_CHECK(F >= 1 && F <= kAssembleMaxF, "assemble_features: F = ", F, " outside 1 .. ", kAssembleMaxF);
-  const bool has_c = codes.has_value() && codes->defined() && codes->numel() > 0;
-  const bool has_q = cont.has_value() && cont->defined() && cont->numel() > 0;
   int64_t C = 0, Q = 0;
   if (has_c) {
     check_t(*codes, at::kInt, "codes");
@@ -1050,26 +1036,6 @@ static void assemble_features_impl(const c10::optional<at::Tensor>& codes, const
                      : wf::launch_assemble_features_f32(cp, xp, off, size, mu, sd, N, (int)C, (int)Q, (int)F, (int)ld,
                                                         fp(out), cur_stream(), pm);
   TORCH_CHECK(ok, "assemble_features: the launcher refused the shape");
-}
-
-void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
-                       c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
-                       c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t N, int64_t F,
-                       const at::Tensor& out) {
-  assemble_features_impl(codes, cont, cat_off, cat_size, mean, stdv, 0, N, N, F, out, -1, c10::nullopt);
-}
-
-// Rows [row0, row0 + N) of resident source columns ([C][Ntot] / [Q][Ntot], read in place), with
-// source column perm_col (or -1) read through perm: the permutation-importance pass.
-void assemble_features_rows(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
-                            c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
-                            c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t row0, int64_t N,
-                            int64_t F, const at::Tensor& out, int64_t perm_col, c10::optional<at::Tensor> perm) {
-  int64_t Ntot = -1;
-  if (codes.has_value() && codes->defined() && codes->numel() > 0 && codes->dim() == 2) Ntot = codes->size(1);
-  else if (cont.has_value() && cont->defined() && cont->numel() > 0 && cont->dim() == 2) Ntot = cont->size(1);
-  TORCH_CHECK(Ntot >= 1, "assemble_features: no source columns");
-  assemble_features_impl(codes, cont, cat_off, cat_size, mean, stdv, row0, N, Ntot, F, out, perm_col, perm);
 }
 
 // Scoring-error sums (score.hip): out[slot] = {sum d^2, sum |d|}, d = pred * y_scale + y_shift - y
@@ -1252,12 +1218,6 @@ void cnn_sgd_pack(const at::Tensor& p, const at::Tensor& g, const at::Tensor& ve
                           (float)gscale, zero_g ? 1 : 0, d, bfp(WcA), bfp(WdF), bfp(WdB), cur_stream(), clip_state(clip),
                           (float)clipvalue);
 }
-void cnn_sgd_pack_noclip(const at::Tensor& p, const at::Tensor& g, const at::Tensor& vel, const at::Tensor& step,
-                         double lr, double decay, double momentum, bool nesterov, double gscale, bool zero_g,
-                         const std::vector<int64_t>& dims, const at::Tensor& WcA, const at::Tensor& WdF,
-                         const at::Tensor& WdB) {
-  cnn_sgd_pack(p, g, vel, step, lr, decay, momentum, nesterov, gscale, zero_g, dims, WcA, WdF, WdB, c10::nullopt, 0.0);
-}
 
 static const long long* rng_ptr(const c10::optional<at::Tensor>& rng) {
   if (!rng.has_value() || !rng->defined()) return nullptr;
@@ -1380,8 +1340,6 @@ struct Checked<F> {
 }  // namespace
 
 #define WF_DEF(name) m.def(#name, &Checked<&name>::call)
-// a second overload of `name` (e.g. the call shape from before the trailing clip arguments)
-#define WF_DEF_AS(name, fn) m.def(#name, &Checked<&fn>::call)
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "wellflow HIP kernel library (gfx950)";
@@ -1404,7 +1362,6 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(lstm_backward_dw);
   WF_DEF(lstm_pack_weights);
   WF_DEF(lstm_adam_pack);
-  WF_DEF_AS(lstm_adam_pack, lstm_adam_pack_noclip);
   WF_DEF(head_fwd);
   WF_DEF(head_bwd_w);
   WF_DEF(head_fwd_bwd);
@@ -1412,17 +1369,14 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(loss);
   WF_DEF(adam);
   WF_DEF(adam_dev);
-  WF_DEF_AS(adam_dev, adam_dev_noclip);
   WF_DEF(sgd);
   WF_DEF(sgd_dev);
-  WF_DEF_AS(sgd_dev, sgd_dev_noclip);
   WF_DEF(grad_clip_scale);
   WF_DEF(cast_bf16);
   WF_DEF(gather_rows);
   WF_DEF(transpose_cast_bf16);
   WF_DEF(im2col1d);
   WF_DEF(assemble_features);
-  WF_DEF_AS(assemble_features, assemble_features_rows);  // + row range and one permuted source column
   WF_DEF(err_sums);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
@@ -1430,7 +1384,6 @@ PYBIND11_MODULE(_C, m) {
   m.def("cnn_part_sizes", &cnn_part_sizes);
   WF_DEF(cnn_pack);
   WF_DEF(cnn_sgd_pack);
-  WF_DEF_AS(cnn_sgd_pack, cnn_sgd_pack_noclip);
   WF_DEF(cnn_forward);
   WF_DEF(cnn_backward);
   WF_DEF(cnn_reduce);

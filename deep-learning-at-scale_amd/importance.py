@@ -30,12 +30,9 @@ import sys
 import numpy as np
 import torch
 
-from .config import build_parser, config_from_namespace
-from .data.features import SeriesWindows, window_starts
-from .data.io import load_table
-from .data.schema import parse_schema
 from .models.gilbert import GilbertModel
-from .predict import HBM_TABLE_FRACTION, Predictor, _numeric_target
+from .predict import Predictor, _numeric_target, scoring_job
+from .scoring import LstmPass, MlpPass, permuted
 
 GILBERT_INPUTS = ("whp", "choke", "glr")
 CSV_COLUMNS = ("column", "kind", "baseline_mse", "permuted_mse_mean", "permuted_mse_std", "importance", "ratio",
@@ -52,7 +49,7 @@ class PermutationImportance:
     Without ``perms`` they are drawn by ``torch.randperm`` from a ``torch.Generator`` seeded with
     ``seed`` on the device that scores, in (column, repeat) order.
     ``piece_rows``: rows of the assembled MLP table per piece on the native path (0 = what fits
-    in 1/8 of HBM, as ``Predictor._predict_mlp``); rounded down to whole engine batches."""
+    in 1/8 of HBM, as the prediction job; scoring.py); rounded down to whole engine batches."""
 
     def __init__(self, predictor: Predictor, repeats: int = 5, seed: int = 0, piece_rows: int = 0):
         if predictor.name == "cnn":
@@ -124,10 +121,8 @@ class PermutationImportance:
             raise TypeError("perms: a tensor [columns][repeats][rows] or a callable (column, repeat) -> perm")
         if pred.name == "gilbert":
             scorer = _GilbertScorer(pred, table, y)
-        elif pred.name == "lstm":
-            scorer = _LstmScorer(pred, table, y, n)
         else:
-            scorer = _MlpScorer(pred, table, y, n, self.piece_rows)
+            scorer = LearnedScorer(pred, table, y, self.piece_rows)
         if scorer.M < 1:
             raise ValueError(f"no row can be scored: every series is shorter than the window of {pred.seq_len} rows")
         gen = None
@@ -179,12 +174,6 @@ def _err_sums_host(p, y64, y_scale: float, y_shift: float):
     return float(np.sum(d * d)), float(np.sum(np.abs(d)))
 
 
-def _permuted(table: dict, col: str, perm) -> dict:
-    t = dict(table)
-    t[col] = np.asarray(table[col])[np.asarray(perm, dtype=np.int64)]
-    return t
-
-
 class _Scorer:
     """One table, scored again and again with one column permuted. ``score(slot, k, perm)``
     leaves the pass's {sum d^2, sum |d|} in ``slot``; ``finish()`` returns them all."""
@@ -210,35 +199,33 @@ class _GilbertScorer(_Scorer):
         self.y, self.M = y64, len(y64)
 
     def score(self, slot, k, perm):
-        cols = self.cols if k < 0 else _permuted(self.cols, GILBERT_INPUTS[k], perm.numpy())
+        cols = self.cols if k < 0 else permuted(self.cols, GILBERT_INPUTS[k], perm.numpy())
         self.sums[slot] = _err_sums_host(self.model.predict(cols), self.y, 1.0, 0.0)
 
 
-class _LearnedScorer(_Scorer):
-    """Shared by the MLP and the LSTM: the target scale, the column names, the host path."""
+class LearnedScorer(_Scorer):
+    """The MLP and the LSTM: one pass of scoring.py per ``score``, then the error sums — on the
+    device (csrc/score.hip) when the pass assembles there, else in numpy. LSTM: the column is
+    permuted over the series-sorted row table; target: the raw target at each window's last row."""
 
-    def __init__(self, pred, y64):
+    def __init__(self, pred, table, y64, piece_rows: int = 0):
         pipe = pred.pipe
-        self.pred, self.pipe = pred, pipe
+        if pred.name == "lstm":
+            ps = LstmPass(pred, table, "LSTM importance scoring")
+        else:
+            ps = MlpPass(pred, table, "MLP importance scoring", resident=True, piece_rows=piece_rows)
+        self.pred, self.ps, self.M, self.native, self.on_device = pred, ps, ps.M, ps.native, ps.on_device
         self.y_scale, self.y_shift = (float(pipe.y_std), float(pipe.y_mean)) if pipe.standardize_target else (1.0, 0.0)
-        self.names = [ix.column for ix in pipe.indexers] + list(pipe.continuous)
         self.y32 = y64.astype(np.float32)  # the kernel's target format; the oracle scores against the same values
-
-    def _device_side(self, what: str) -> bool:
-        self.native = self.pred.native
-        self.on_device = self.native and self.pred._device_assembly(what)
+        if ps.rows is not None:
+            self.y32 = self.y32[ps.rows]
+        self.y64 = self.y32.astype(np.float64)
         if self.on_device:
-            self.perm_device, self.perm_dtype = self.pred.device, torch.int32
-        return self.on_device
+            from .ops.native import err_sums_scratch
 
-    def _resident(self, table):
-        from .ops.native import ResidentColumns, err_sums_scratch
-
-        pipe = self.pipe
-        codes, cont = pipe.raw_columns(table)
-        self.res = ResidentColumns(codes, cont, *pipe.block_spec(), *pipe.scale(), self.pred.n_features,
-                                   self.pred.device)
-        self.scratch = err_sums_scratch(self.pred.device)
+            self.perm_device, self.perm_dtype = pred.device, torch.int32
+            self.scratch = err_sums_scratch(pred.device)
+            self.y_dev = torch.from_numpy(self.y32).to(pred.device)
 
     def begin(self, passes):
         if self.on_device:
@@ -247,107 +234,20 @@ class _LearnedScorer(_Scorer):
             super().begin(passes)
 
     def finish(self):
-        eng = self.pred.eng
-        if hasattr(eng, "check_device_errors"):
-            eng.check_device_errors()
+        self.pred.eng.check_device_errors()
         return self.out.cpu().numpy() if self.on_device else self.sums
 
-    def _reduce(self, slot):
+    def reduce(self, slot):
         from .ops.native import err_sums
 
-        err_sums(self.p, self.y_dev, self.y_scale, self.y_shift, self.out, slot, self.scratch)
-
-
-class _MlpScorer(_LearnedScorer):
-    def __init__(self, pred, table, y64, n, piece_rows):
-        super().__init__(pred, y64)
-        self.table, self.M, self.n = table, n, n
-        self.eng = pred._engine(n)
-        self.B = B = pred.eng_batch
-        self.y64 = self.y32.astype(np.float64)
-        if not self._device_side("MLP importance scoring"):
-            return
-        dev = pred.device
-        self._resident(table)
-        if piece_rows <= 0:
-            piece_rows = torch.cuda.get_device_properties(dev).total_memory // HBM_TABLE_FRACTION // (self.eng.Fp * 2)
-        self.piece = max(B, piece_rows // B * B)
-        self.X = torch.empty((min(self.piece, n), self.eng.Fp), dtype=torch.bfloat16, device=dev)
-        self.p = torch.empty(n, device=dev)
-        self.y_dev = torch.from_numpy(self.y32).to(dev)
+        err_sums(self.ps.p, self.y_dev, self.y_scale, self.y_shift, self.out, slot, self.scratch)
 
     def score(self, slot, k, perm):
-        eng, B, n = self.eng, self.B, self.n
+        p = self.ps.score(k, perm)
         if self.on_device:
-            for a in range(0, n, self.piece):
-                b = min(n, a + self.piece)
-                X = self.res.assemble(torch.bfloat16, rows=(a, b), perm=None if k < 0 else perm[a:b],
-                                      perm_col=k, out=self.X[: b - a])
-                for c in range(0, b - a, B):  # [chunk][Fp] slices read in place; the last one may be short
-                    self.p[a + c : min(a + c + B, b)].copy_(eng.forward(X[c : c + B]))
-            self._reduce(slot)
-            return
-        tab = self.table if k < 0 else _permuted(self.table, self.names[k], perm.cpu().numpy())
-        X = torch.from_numpy(self.pipe.features(tab))
-        p = np.empty(n, np.float32)
-        for a in range(0, n, B):
-            xb = X[a : a + B]
-            if self.native:  # F > 512: host assembly, the native engine
-                xb = eng.to_input_format(xb).to(self.pred.device)
-            p[a : a + B] = eng.forward(xb).float().cpu().numpy()
-        self.sums[slot] = _err_sums_host(p, self.y64, self.y_scale, self.y_shift)
-
-
-class _LstmScorer(_LearnedScorer):
-    """The column is permuted over the series-sorted row table; the windows are then read in
-    place (Predictor._lstm_windows_native). Target: the raw target at each window's last row."""
-
-    def __init__(self, pred, table, y64, n):
-        super().__init__(pred, y64)
-        T, self.n = pred.seq_len, n
-        self.T = T
-        self.table, ids, order = pred._sorted_series(table, n)
-        self.starts = np.asarray(window_starts(n, T, ids), np.int64)
-        self.M = W = len(self.starts)
-        if W < 1:
-            return
-        last = self.starts + T - 1
-        self.y32 = self.y32[order][last]
-        self.y64 = self.y32.astype(np.float64)
-        self.eng = pred._engine(W)
-        self.B = B = pred.eng_batch
-        if not self._device_side("LSTM importance scoring"):
-            return
-        dev = pred.device
-        self._resident(self.table)
-        self.rows = torch.empty((n, pred.n_features), dtype=torch.float32, device=dev)
-        self.win = SeriesWindows(self.rows, torch.from_numpy(self.starts).to(dev), T)
-        # window ids per engine launch, the last chunk padded by repeating a valid id
-        self.chunks = [(a, min(B, W - a), torch.arange(a, a + B, device=dev).clamp_(max=min(a + B, W) - 1))
-                       for a in range(0, W, B)]
-        self.p = torch.empty(W, device=dev)
-        self.y_dev = torch.from_numpy(self.y32).to(dev)
-
-    def score(self, slot, k, perm):
-        eng, B, W = self.eng, self.B, self.M
-        if self.on_device:
-            self.res.assemble(torch.float32, perm=None if k < 0 else perm, perm_col=k, out=self.rows)
-            for a, m, ids in self.chunks:
-                self.p[a : a + m].copy_(eng.forward_windows(self.win, ids)[:m])
-            self._reduce(slot)
-            return
-        tab = self.table if k < 0 else _permuted(self.table, self.names[k], perm.cpu().numpy())
-        win = SeriesWindows(self.pipe.features(tab), self.starts, self.T)
-        p = np.empty(W, np.float32)
-        for a in range(0, W, B):
-            xb = torch.from_numpy(np.ascontiguousarray(win[np.arange(a, min(a + B, W))]))
-            m = xb.shape[0]
-            if self.native:  # F > 512: host assembly, the native engine (whole batches of 64-row tiles)
-                if m < B:
-                    xb = torch.cat([xb, xb[-1:].expand(B - m, -1, -1)])
-                xb = xb.to(self.pred.device)
-            p[a : a + m] = eng.forward(xb)[:m].float().cpu().numpy()
-        self.sums[slot] = _err_sums_host(p, self.y64, self.y_scale, self.y_shift)
+            self.reduce(slot)
+        else:
+            self.sums[slot] = _err_sums_host(torch.as_tensor(p).cpu().numpy(), self.y64, self.y_scale, self.y_shift)
 
 
 # ---------------------------------------------------------------------- the job
@@ -364,28 +264,16 @@ def _write_csv(path: str, rows: list) -> None:
 
 
 def run_importance(model: str, argv, log=print) -> dict:
-    ap = build_parser(model)
-    ap.prog = f"python -m wellflow.importance {model}"
-    ap.description = ("Usage: python -m wellflow.importance <model> columnNames columnTypes targetColumn storagePath "
-                      "dataPath (the data: held-out rows)")
-    ap.add_argument("--repeats", type=int, default=5, help="shuffles per column (default 5)")
-    ap.add_argument("--columns", default=None, help="comma-separated input columns (default: all)")
-    ap.add_argument("--out", default=None, help="importance CSV (default <storagePath>importance/<model>.csv)")
-    ns = ap.parse_args(list(argv))
-    cfg = config_from_namespace(model, ns)
-    sp = cfg.storage_path
-    if sp and not sp.endswith(("/", os.sep)):
-        sp += os.sep
-    out_path = ns.out or os.path.join(sp + "importance", f"{model}.csv")
+    def add_arguments(ap):
+        ap.add_argument("--repeats", type=int, default=5, help="shuffles per column (default 5)")
+        ap.add_argument("--columns", default=None, help="comma-separated input columns (default: all)")
+
+    ns, cfg, schema, out_path, load_predictor, load_data = scoring_job(
+        "importance", "importance", "importance", "dataPath (the data: held-out rows)", model, argv, add_arguments)
     if int(os.environ.get("RANK", "0")) != 0:  # one process on one device: rank 0 alone works and writes
         return {"model": model, "out": out_path, "skipped": True}
-    schema = parse_schema(cfg.column_names, cfg.column_types)
-    pred = Predictor.load(cfg.mdl_path(model), schema, device=cfg.device, precision=cfg.precision,
-                          seq_len=cfg.seq_len, group_col=cfg.group_col,
-                          batch=cfg.batch_size if ns.batch_size is not None else 0)
-    job = PermutationImportance(pred, repeats=ns.repeats, seed=cfg.seed)
-    table = load_table(cfg.data, schema, header=cfg.header, synth_wells=cfg.synth_wells,
-                       synth_steps=cfg.synth_steps, seed=cfg.seed)
+    job = PermutationImportance(load_predictor(), repeats=ns.repeats, seed=cfg.seed)
+    table = load_data()
     columns = [c.strip() for c in ns.columns.split(",") if c.strip()] if ns.columns is not None else None
     result = job.run(table, columns=columns, target=cfg.target)
     result["out"] = out_path

@@ -55,6 +55,9 @@ class TorchEngine:
     def sync_weights(self) -> None:  # parameters ARE views of the flat buffer
         pass
 
+    def check_device_errors(self) -> None:  # no persistent launches, so nothing to report
+        pass
+
     def train(self, mode: bool = True):
         self.module.train(mode)
 

@@ -46,48 +46,21 @@ def assemble_features(codes, cont, cat_off, cat_size, mean, std, n_features: int
     no widened [N][F] matrix crosses the bus), ``cat_off`` / ``cat_size`` [C] and ``mean`` /
     ``std`` [Q] from :meth:`FeaturePipeline.block_spec` / :meth:`~FeaturePipeline.scale`.
     ``out_dtype`` bf16 -> [N][round_up(F, 8)], the MLP input format; float32 -> [N][F], the LSTM
-    row table (``out``: write into this tensor). The block spec is checked here, on the host, before
-    anything is launched."""
-    import numpy as np
+    row table (``out``: write into this tensor). One upload and one assembly of
+    :class:`ResidentColumns`, which checks the block spec on the host before anything is launched;
+    an empty table gives an empty result without a launch."""
     import torch
 
-    dev = torch.device(device)
-    F = int(n_features)
-    off = np.asarray(cat_off, dtype=np.int64).reshape(-1)
-    size = np.asarray(cat_size, dtype=np.int64).reshape(-1)
-    codes = torch.as_tensor(codes)
-    cont = torch.as_tensor(cont)
-    C, Q = (codes.shape[0] if codes.numel() else 0), (cont.shape[0] if cont.numel() else 0)
-    N = codes.shape[1] if C else (cont.shape[1] if Q else 0)
-    if len(off) != C or len(size) != C:
-        raise ValueError(f"assemble_features: {C} code columns but {len(off)} offsets / {len(size)} sizes")
-    if C and ((size < 0).any() or (off != np.cumsum(size) - size).any()):
-        raise ValueError("assemble_features: one-hot blocks must be back to back from column 0")
-    if int(size.sum()) + Q != F:
-        raise ValueError(f"assemble_features: one-hot width {int(size.sum())} + {Q} continuous != F = {F}")
-    if Q and (cont.shape[1] != N or len(mean) != Q or len(std) != Q):
-        raise ValueError("assemble_features: cont / mean / std shapes disagree")
-    i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
-    f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
-    ld = (F + 7) // 8 * 8 if out_dtype == torch.bfloat16 else F
-    if N < 1:
-        return torch.zeros((0, ld), dtype=out_dtype, device=dev)
-    if out is None:
-        out = torch.empty((N, ld), dtype=out_dtype, device=dev)
-    elif out.shape != (N, ld) or out.dtype != out_dtype:
-        raise ValueError(f"assemble_features: out must be {out_dtype} [{N}][{ld}]")
-    lib().assemble_features(codes.to(dev, torch.int32).contiguous() if C else None,
-                            cont.to(dev, torch.float32).contiguous() if Q else None,
-                            i32(off) if C else None, i32(size) if C else None,
-                            f32(mean) if Q else None, f32(std) if Q else None, N, F, out)
-    return out
+    res = ResidentColumns(codes, cont, cat_off, cat_size, mean, std, n_features, device)
+    if res.N < 1:
+        return torch.zeros((0, res.out_width(out_dtype)), dtype=out_dtype, device=res.device)
+    return res.assemble(out_dtype, out=out)
 
 
 class ResidentColumns:
-    """A table's raw columns and its pipeline's block spec, uploaded ONCE: what the passes of a
-    permutation-importance run (wellflow/importance.py) assemble from, over and over, without a
-    further host check or H2D copy. The spec is checked here, on the host, as
-    :func:`assemble_features` checks it."""
+    """A table's raw columns and its pipeline's block spec, checked on the host and uploaded ONCE:
+    what the passes of a permutation-importance run (wellflow/importance.py) assemble from, over
+    and over, without a further host check or H2D copy."""
 
     def __init__(self, codes, cont, cat_off, cat_size, mean, std, n_features: int, device):
         import numpy as np
@@ -98,8 +71,8 @@ class ResidentColumns:
         off = np.asarray(cat_off, dtype=np.int64).reshape(-1)
         size = np.asarray(cat_size, dtype=np.int64).reshape(-1)
         codes, cont = torch.as_tensor(codes), torch.as_tensor(cont)
-        self.C = C = codes.shape[0] if codes.numel() else 0
-        self.Q = Q = cont.shape[0] if cont.numel() else 0
+        self.C = C = codes.shape[0] if codes.dim() == 2 else 0
+        self.Q = Q = cont.shape[0] if cont.dim() == 2 else 0
         self.N = codes.shape[1] if C else (cont.shape[1] if Q else 0)
         if len(off) != C or len(size) != C:
             raise ValueError(f"assemble_features: {C} code columns but {len(off)} offsets / {len(size)} sizes")
@@ -109,8 +82,6 @@ class ResidentColumns:
             raise ValueError(f"assemble_features: one-hot width {int(size.sum())} + {Q} continuous != F = {F}")
         if Q and (cont.shape[1] != self.N or len(mean) != Q or len(std) != Q):
             raise ValueError("assemble_features: cont / mean / std shapes disagree")
-        if self.N < 1:
-            raise ValueError("assemble_features: no rows")
         if self.N >= 2 ** 31:
             raise ValueError(f"assemble_features: an int32 permutation cannot index {self.N} rows")
         i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731

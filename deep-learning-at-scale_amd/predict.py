@@ -11,9 +11,8 @@ writes one prediction per row, in raw target units, next to the echoed input col
 
 A scoring job touches every row once, so on the native path the features are assembled ON THE
 DEVICE from the raw columns (csrc/features.hip: label codes + continuous values -> the engine's
-input rows), not widened on the host and uploaded: the MLP reads ``[chunk][Fp]`` bf16 slices of
-that table in place, the LSTM reads its windows in place from the fp32 row table
-(:meth:`NativeLSTM.forward_windows`).
+input rows), not widened on the host and uploaded: one pass of scoring.py, which the
+permutation-importance job (importance.py) runs again and again.
 """
 from __future__ import annotations
 
@@ -24,16 +23,15 @@ import numpy as np
 import torch
 
 from .config import MODEL_DEFAULTS, RunConfig, build_parser, config_from_namespace
-from .data.features import FeaturePipeline, SeriesWindows, take, window_starts
+from .data.features import FeaturePipeline, take, window_starts
 from .data.io import load_table
 from .data.pipeline import _group_ids
 from .data.schema import Schema, parse_schema
 from .models import registry
 from .models.base import note_slow_path
 from .models.gilbert import GilbertModel
+from .scoring import LstmPass, MlpPass
 from .utils import checkpoint as ckpt
-
-HBM_TABLE_FRACTION = 8  # an assembled table above 1/8 of HBM is uploaded and scored chunk by chunk
 
 
 def _round_up(x: int, m: int) -> int:
@@ -73,6 +71,7 @@ class Predictor:
         self.eng = None
         self.cfg: RunConfig | None = None
         self.seq_len, self.group_col = 0, ""
+        self.piece_rows = 0  # rows of the assembled MLP table per piece (0: what fits in 1/8 of HBM; scoring.py)
 
     # ------------------------------------------------------------------ loading
     @classmethod
@@ -150,7 +149,8 @@ class Predictor:
     # ------------------------------------------------------------------ scoring
     def predict_table(self, table: dict):
         """Predictions in raw target units, aligned with the table's rows in their given order
-        (NaN where a row has no prediction). ``cnn``: ``(window_end_row [W], forecasts [W][O])``."""
+        (NaN where a row has no prediction: no window ends there). ``cnn``:
+        ``(window_end_row [W], forecasts [W][O])``."""
         n = len(next(iter(table.values()))) if table else 0
         if self.name == "gilbert":
             need = [k for k in ("whp", "choke", "glr") if k not in table]
@@ -160,12 +160,18 @@ class Predictor:
             return model.predict({k: np.asarray(table[k], np.float64) for k in ("whp", "choke", "glr")})
         if self.name == "cnn":
             return self._predict_cnn(table, n)
+        out = np.full(n, np.nan, np.float32)
         if n == 0:
-            return np.zeros(0, np.float32)
-        with torch.no_grad():
-            out = self._predict_lstm(table, n) if self.name == "lstm" else self._predict_mlp(table, n)
-        if hasattr(self.eng, "check_device_errors"):
+            return out
+        ps = LstmPass(self, table) if self.name == "lstm" else MlpPass(self, table, piece_rows=self.piece_rows)
+        if ps.M:
+            with torch.no_grad():
+                p = ps.score()
+            p = np.asarray(self.pipe.inverse_target(torch.as_tensor(p).cpu().numpy()), np.float32)
             self.eng.check_device_errors()
+            if ps.rows is None:
+                return p
+            out[ps.rows] = p
         return out
 
     def _device_assembly(self, what: str) -> bool:
@@ -178,40 +184,6 @@ class Predictor:
                        f"F={self.n_features}")
         return False
 
-    def _predict_mlp(self, table: dict, n: int) -> np.ndarray:
-        eng = self._engine(n)
-        B = self.eng_batch
-        if not self.native:
-            X = torch.from_numpy(self.pipe.features(table))
-            out = torch.empty(n)
-            for a in range(0, n, B):
-                out[a : a + B] = eng.forward(X[a : a + B]).float().cpu()
-            return np.asarray(self.pipe.inverse_target(out.numpy()), np.float32)
-        from .ops.native import assemble_features
-
-        pipe, dev = self.pipe, self.device
-        on_device = self._device_assembly("MLP scoring")
-        if on_device:
-            codes, cont = pipe.raw_columns(table)
-            off, size = pipe.block_spec()
-            mean, std = pipe.scale()
-        else:
-            X = pipe.features(table)
-        # an assembled table above 1/8 of HBM: upload and score it in pieces of whole engine batches
-        limit = torch.cuda.get_device_properties(dev).total_memory // HBM_TABLE_FRACTION
-        piece = max(B, limit // (eng.Fp * 2) // B * B)
-        out = torch.empty(n, device=dev)
-        for a in range(0, n, piece):
-            b = min(n, a + piece)
-            if on_device:
-                Xd = assemble_features(codes[:, a:b], cont[:, a:b], off, size, mean, std, self.n_features,
-                                       torch.bfloat16, dev)
-            else:
-                Xd = eng.to_input_format(torch.from_numpy(X[a:b])).to(dev)
-            for c in range(0, b - a, B):  # [chunk][Fp] slices read in place; the last one may be short
-                out[a + c : min(a + c + B, b)].copy_(eng.forward(Xd[c : c + B]))
-        return np.asarray(pipe.inverse_target(out.cpu().numpy()), np.float32)
-
     def _sorted_series(self, table: dict, n: int):
         """Rows grouped into series as training grouped them (stable sort: file order is time
         order inside a series): (sorted table, series id per sorted row, order)."""
@@ -220,48 +192,6 @@ class Predictor:
             return table, None, np.arange(n)
         order = np.argsort(ids, kind="stable")
         return take(table, order), ids[order], order
-
-    def _predict_lstm(self, table: dict, n: int) -> np.ndarray:
-        T = self.seq_len
-        stable, ids, order = self._sorted_series(table, n)
-        starts = np.asarray(window_starts(n, T, ids), np.int64)
-        W = len(starts)
-        pred_sorted = np.full(n, np.nan, np.float32)
-        if W:
-            eng = self._engine(W)
-            B = self.eng_batch
-            if self.native:
-                p = self._lstm_windows_native(stable, starts, eng, B)
-            else:
-                win = SeriesWindows(self.pipe.features(stable), starts, T)
-                p = torch.empty(W)
-                for a in range(0, W, B):
-                    xb = torch.from_numpy(np.ascontiguousarray(win[np.arange(a, min(a + B, W))]))
-                    p[a : a + B] = eng.forward(xb).float().cpu()
-                p = p.numpy()
-            pred_sorted[starts + T - 1] = self.pipe.inverse_target(p)  # a window predicts its last row
-        out = np.empty(n, np.float32)
-        out[order] = pred_sorted
-        return out
-
-    def _lstm_windows_native(self, stable: dict, starts: np.ndarray, eng, B: int) -> np.ndarray:
-        from .ops.native import assemble_features
-
-        pipe, dev = self.pipe, self.device
-        if self._device_assembly("LSTM scoring"):
-            codes, cont = pipe.raw_columns(stable)
-            rows = assemble_features(codes, cont, *pipe.block_spec(), *pipe.scale(), self.n_features,
-                                     torch.float32, dev)
-        else:
-            rows = torch.from_numpy(pipe.features(stable)).to(dev)
-        win = SeriesWindows(rows, torch.from_numpy(starts).to(dev), self.seq_len)
-        W = len(starts)
-        out = torch.empty(W, device=dev)
-        for a in range(0, W, B):
-            m = min(B, W - a)
-            ids = torch.arange(a, a + B, device=dev).clamp_(max=a + m - 1)  # padded by repeating a valid id
-            out[a : a + m].copy_(eng.forward_windows(win, ids)[:m])  # ... and the padding dropped
-        return out.cpu().numpy()
 
     def _predict_cnn(self, table: dict, n: int):
         L, O = self.cfg.cnn_input_len, self.cfg.cnn_outputs
@@ -282,8 +212,7 @@ class Predictor:
                 for a in range(0, W, B):
                     p = eng.forward(torch.from_numpy(X[a : a + B]).to(self.device))
                     fc[a : a + B] = p.float().reshape(-1, O).cpu().numpy()
-            if hasattr(eng, "check_device_errors"):
-                eng.check_device_errors()
+            eng.check_device_errors()
             fc = np.asarray(self.pipe.inverse_target(fc), np.float32)
         return end_rows, fc
 
@@ -340,19 +269,42 @@ def _write_csv(path: str, table: dict, names: list, pred_cols: dict, header: boo
     os.replace(tmp, path)
 
 
-def run_predict(model: str, argv, log=print) -> dict:
+def scoring_job(module: str, noun: str, kind: str, usage: str, model: str, argv, add_arguments=None):
+    """The front matter of a job that scores a saved model (``python -m wellflow.<module>``): the
+    parser (+ the job's own arguments, + ``--out``), the run configuration and the schema.
+    Returns ``(ns, cfg, schema, out_path, load_predictor, load_data)``; ``out_path``, the ``noun``
+    CSV, defaults to ``<storagePath><kind>/<model>.csv``."""
     ap = build_parser(model)
-    ap.prog = f"python -m wellflow.predict {model}"
-    ap.description = "Usage: python -m wellflow.predict <model> columnNames columnTypes targetColumn storagePath dataPath"
-    ap.add_argument("--out", default=None, help="prediction CSV (default <storagePath>predictions/<model>.csv)")
+    ap.prog = f"python -m wellflow.{module} {model}"
+    ap.description = f"Usage: python -m wellflow.{module} <model> columnNames columnTypes targetColumn storagePath {usage}"
+    if add_arguments is not None:
+        add_arguments(ap)
+    ap.add_argument("--out", default=None, help=f"{noun} CSV (default <storagePath>{kind}/<model>.csv)")
     ns = ap.parse_args(list(argv))
     cfg = config_from_namespace(model, ns)
     schema = parse_schema(cfg.column_names, cfg.column_types)
-    pred = Predictor.load(cfg.mdl_path(model), schema, device=cfg.device, precision=cfg.precision,
-                          seq_len=cfg.seq_len, group_col=cfg.group_col,
-                          batch=cfg.batch_size if ns.batch_size is not None else 0)
-    table = load_table(cfg.data, schema, header=cfg.header, synth_wells=cfg.synth_wells,
-                       synth_steps=cfg.synth_steps, seed=cfg.seed)
+    sp = cfg.storage_path
+    if sp and not sp.endswith(("/", os.sep)):
+        sp += os.sep
+    out_path = ns.out or os.path.join(sp + kind, f"{model}.csv")
+
+    def load_predictor() -> Predictor:
+        return Predictor.load(cfg.mdl_path(model), schema, device=cfg.device, precision=cfg.precision,
+                              seq_len=cfg.seq_len, group_col=cfg.group_col,
+                              batch=cfg.batch_size if ns.batch_size is not None else 0)
+
+    def load_data() -> dict:
+        return load_table(cfg.data, schema, header=cfg.header, synth_wells=cfg.synth_wells,
+                          synth_steps=cfg.synth_steps, seed=cfg.seed)
+
+    return ns, cfg, schema, out_path, load_predictor, load_data
+
+
+def run_predict(model: str, argv, log=print) -> dict:
+    _, cfg, schema, out_path, load_predictor, load_data = scoring_job(
+        "predict", "prediction", "predictions", "dataPath", model, argv)
+    pred = load_predictor()
+    table = load_data()
     n = len(table[schema.names[0]])
     dropped = 0
     if cfg.data not in ("synth", "synthetic", ""):
@@ -381,10 +333,6 @@ def run_predict(model: str, argv, log=print) -> dict:
             result["mse"] = float(np.mean(d * d))
         result["predictions"] = p
     result.update(scored=scored, unscored=n - scored)
-    sp = cfg.storage_path
-    if sp and not sp.endswith(("/", os.sep)):
-        sp += os.sep
-    out_path = ns.out or os.path.join(sp + "predictions", f"{model}.csv")
     result["out"] = out_path
     if int(os.environ.get("RANK", "0")) == 0:
         _write_csv(out_path, table, schema.names, pred_cols, cfg.header)

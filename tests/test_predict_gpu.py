@@ -129,12 +129,16 @@ def test_assemble_features_widest_table_and_refusals():
         assemble_features(codes, cont[:2], [3], [4], mean[:2], std[:2], 6, torch.float32, DEV)
     with pytest.raises(ValueError, match="F = 9"):
         assemble_features(codes, cont[:2], [0], [4], mean[:2], std[:2], 9, torch.float32, DEV)
+    # an empty table: an empty result of the asked dtype and width, nothing launched
+    for dt, ld in ((torch.float32, 6), (torch.bfloat16, 8)):
+        empty = assemble_features(codes[:, :0], cont[:2, :0], [0], [4], mean[:2], std[:2], 6, dt, DEV)
+        assert empty.shape == (0, ld) and empty.dtype == dt and empty.device == DEV
 
 
 # ------------------------------------------------------------------ 2. MLP scoring
-def test_native_mlp_scoring_two_chunks(tmp_path):
+def _mlp_case(tmp_path):
+    """1000 rows, F = 18, a saved 18-256-256-1 MLP: (schema, table, pipe, ref, .mdl path)."""
     from wellflow.models.mlp import MLPRegressor
-    from wellflow.predict import Predictor
 
     schema = parse_schema(NAMES, TYPES)
     table = load_table("synth", schema, synth_wells=8, synth_steps=125, seed=3)
@@ -144,6 +148,13 @@ def test_native_mlp_scoring_two_chunks(tmp_path):
     ref = MLPRegressor(18, (256, 256))
     p = str(tmp_path / "models" / "mlp.mdl")
     save_mdl(p, "mlp", registry.keras_layers("mlp", ref), {"features": pipe.state()})
+    return schema, table, pipe, ref, p
+
+
+def test_native_mlp_scoring_two_chunks(tmp_path):
+    from wellflow.predict import Predictor
+
+    schema, table, pipe, ref, p = _mlp_case(tmp_path)
     pred = Predictor.load(p, schema, device="cuda", precision="bf16", batch=512)
     got = pred.predict_table(table)  # 1000 rows: a full chunk of 512 and a short one of 488
     assert pred.native and pred.eng_batch == 512 and got.shape == (1000,) and got.dtype == np.float32
@@ -159,10 +170,38 @@ def test_native_mlp_scoring_two_chunks(tmp_path):
     assert _rel(got, pipe.inverse_target(want)) < 2e-2
 
 
-# ------------------------------------------------------------------ 3. LSTM scoring
-def test_native_lstm_scoring_padded_last_chunk(tmp_path):
-    from wellflow.models.lstm import LSTMRegressor
+def test_native_mlp_scoring_in_pieces(tmp_path):
+    """piece_rows = 512: two pieces, each with its own raw-column upload and assembly, the second
+    a short chunk of 488 rows. The same launches on the same rows as the one-piece run."""
     from wellflow.predict import Predictor
+
+    schema, table, pipe, ref, p = _mlp_case(tmp_path)
+    pred = Predictor.load(p, schema, device="cuda", precision="bf16", batch=512)
+    whole = pred.predict_table(table)
+    pred.piece_rows = 512
+    pieced = pred.predict_table(table)
+    assert pred.native and pred.eng_batch == 512 and pieced.shape == (1000,) and np.isfinite(pieced).all()
+    assert np.array_equal(pieced, whole)
+
+
+def test_native_mlp_host_assembly_equals_device_assembly(tmp_path, monkeypatch):
+    """Above the device assembly's width limit the rows are built on the host and uploaded; the
+    native engine then gives the same predictions bit for bit."""
+    from wellflow.predict import Predictor
+
+    schema, table, pipe, ref, p = _mlp_case(tmp_path)
+    pred = Predictor.load(p, schema, device="cuda", precision="bf16", batch=512)
+    dev = pred.predict_table(table)
+    monkeypatch.setattr("wellflow.ops.native.ASSEMBLE_MAX_F", 8)
+    host = pred.predict_table(table)
+    assert pred.native and dev.shape == (1000,) and np.isfinite(dev).all()
+    assert np.array_equal(host, dev)
+
+
+# ------------------------------------------------------------------ 3. LSTM scoring
+def _lstm_case(tmp_path):
+    """150 rows in 3 interleaved series, T = 8, F = 16, a saved H = 128 LSTM."""
+    from wellflow.models.lstm import LSTMRegressor
 
     T, H, Q = 8, 128, 13
     names = ["well"] + [f"x{i}" for i in range(Q)] + ["y"]
@@ -180,6 +219,13 @@ def test_native_lstm_scoring_padded_last_chunk(tmp_path):
     p = str(tmp_path / "models" / "lstm.mdl")
     save_mdl(p, "lstm", registry.keras_layers("lstm", ref),
              {"features": pipe.state(), "job": {"seq_len": T, "group_col": "well", "hidden": H, "mlp_hidden": [256, 256]}})
+    return schema, table, pipe, ref, p, (T, H, n)
+
+
+def test_native_lstm_scoring_padded_last_chunk(tmp_path):
+    from wellflow.predict import Predictor
+
+    schema, table, pipe, ref, p, (T, H, n) = _lstm_case(tmp_path)
     pred = Predictor.load(p, schema, device="cuda", precision="bf16", batch=64)
     got = pred.predict_table(table)
     eng = pred.eng
@@ -203,6 +249,21 @@ def test_native_lstm_scoring_padded_last_chunk(tmp_path):
     print("lstm scoring max abs err vs fp32:", err)
     assert err < 3e-2, err
     assert eng.persistent_error() == 0, eng.persistent_stats()
+
+
+def test_native_lstm_host_assembly_equals_device_assembly(tmp_path, monkeypatch):
+    """129 windows in batches of 64 (the last chunk: one window + padding), the row table built on
+    the host and uploaded: bit-identical to the device-assembled one, NaN in the same rows."""
+    from wellflow.predict import Predictor
+
+    schema, table, pipe, ref, p, (T, H, n) = _lstm_case(tmp_path)
+    pred = Predictor.load(p, schema, device="cuda", precision="bf16", batch=64)
+    dev = pred.predict_table(table)
+    monkeypatch.setattr("wellflow.ops.native.ASSEMBLE_MAX_F", 8)
+    host = pred.predict_table(table)
+    assert pred.native and pred.eng_batch == 64 and (~np.isnan(dev)).sum() == 129
+    assert np.array_equal(host, dev, equal_nan=True)
+    assert pred.eng.persistent_error() == 0, pred.eng.persistent_stats()
 
 
 # ------------------------------------------------------------------ 4. CNN scoring

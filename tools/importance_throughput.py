@@ -38,7 +38,7 @@ if ROOT not in sys.path:
 from wellflow.data.features import FeaturePipeline, take  # noqa: E402
 from wellflow.data.io import load_table  # noqa: E402
 from wellflow.data.schema import parse_schema  # noqa: E402
-from wellflow.importance import _LstmScorer, _MlpScorer  # noqa: E402
+from wellflow.importance import LearnedScorer  # noqa: E402
 from wellflow.models import registry  # noqa: E402
 from wellflow.predict import Predictor  # noqa: E402
 from wellflow.utils.checkpoint import save_mdl  # noqa: E402
@@ -81,13 +81,14 @@ def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
 
 def _measure(pred, table, scorer, cols, passes, host_passes, rounds):
     """Interleaved device / host windows over the columns ``cols`` (source indices), round robin."""
-    n = scorer.n
+    ps = scorer.ps  # the pass (wellflow/scoring.py): its own assembly and forward steps are timed below
+    n = len(table["flow"])
     dev = pred.device
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
     rng = np.random.default_rng(0)
     y = np.asarray(table["flow"], np.float64)
-    names = scorer.names
+    names = ps.names
     scorer.begin(1 + passes)
 
     def device_window():
@@ -121,13 +122,14 @@ def _measure(pred, table, scorer, cols, passes, host_passes, rounds):
     # the terms of one device pass, each alone
     perm = torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)
     k = cols[0]
+    a, b = ps.pieces[0]  # one piece at these sizes
     terms = {"randperm_us": [], "assemble_us": [], "forward_us": [], "reduce_us": []}
     with torch.no_grad():
         for _ in range(max(rounds, 3)):
             terms["randperm_us"].append(_events(lambda: torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)))
-            terms["assemble_us"].append(_events(lambda: scorer.assemble_only(k, perm)))
-            terms["forward_us"].append(_events(scorer.forward_only))
-            terms["reduce_us"].append(_events(lambda: scorer._reduce(0)))
+            terms["assemble_us"].append(_events(lambda: ps.assemble(a, b, k, perm)))
+            terms["forward_us"].append(_events(lambda: ps.forward(ps.X[: b - a], a)))
+            terms["reduce_us"].append(_events(lambda: scorer.reduce(0)))
     rec = {"device": {"pass_s": _median(td), "passes_per_s": 1.0 / _median(td), "all_pass_s": td, "passes_per_window": passes},
            "host": {"pass_s": _median(th), "passes_per_s": 1.0 / _median(th), "all_pass_s": th,
                     "passes_per_window": host_passes},
@@ -135,27 +137,6 @@ def _measure(pred, table, scorer, cols, passes, host_passes, rounds):
            "finite": bool(np.isfinite(sums).all())}
     rec["speedup"] = rec["host"]["pass_s"] / rec["device"]["pass_s"]
     return rec
-
-
-class _TimedMlp(_MlpScorer):
-    def assemble_only(self, k, perm):
-        for a in range(0, self.n, self.piece):
-            b = min(self.n, a + self.piece)
-            self.res.assemble(torch.bfloat16, rows=(a, b), perm=perm[a:b], perm_col=k, out=self.X[: b - a])
-
-    def forward_only(self):  # the table of the last assembly (one piece at these sizes)
-        m = self.X.shape[0]
-        for c in range(0, m, self.B):
-            self.p[c : min(c + self.B, m)].copy_(self.eng.forward(self.X[c : c + self.B]))
-
-
-class _TimedLstm(_LstmScorer):
-    def assemble_only(self, k, perm):
-        self.res.assemble(torch.float32, perm=perm, perm_col=k, out=self.rows)
-
-    def forward_only(self):
-        for a, m, ids in self.chunks:
-            self.p[a : a + m].copy_(self.eng.forward_windows(self.win, ids)[:m])
 
 
 def bench_mlp(rows, passes, host_passes, rounds, tmp):
@@ -169,11 +150,10 @@ def bench_mlp(rows, passes, host_passes, rounds, tmp):
     pipe = FeaturePipeline(schema, "flow", standardize_target=True).fit(take(table, np.arange(0, n, 32)))
     torch.manual_seed(0)
     pred = _predictor(tmp, "mlp", MLPRegressor(pipe.n_features, (256, 256)), pipe, schema)
-    t_setup, scorer = _clock(lambda: _TimedMlp(pred, table, np.asarray(table["flow"], np.float64), n, 0))
-    C, Q = scorer.res.C, scorer.res.Q
-    rec = _measure(pred, table, scorer, list(range(C + Q)), passes, host_passes, rounds)
+    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table, np.asarray(table["flow"], np.float64)))
+    rec = _measure(pred, table, scorer, list(range(len(scorer.ps.names))), passes, host_passes, rounds)
     rec.update(rows=n, features=pipe.n_features, engine_batch=pred.eng_batch, setup_s=t_setup,
-               pieces=(n + scorer.piece - 1) // scorer.piece)
+               pieces=len(scorer.ps.pieces))
     return rec
 
 
@@ -190,9 +170,8 @@ def bench_lstm(passes, host_passes, rounds, tmp):
     torch.manual_seed(0)
     pred = _predictor(tmp, "lstm", LSTMRegressor(pipe.n_features, H), pipe, schema,
                       job={"seq_len": T, "group_col": "well", "hidden": H, "mlp_hidden": [256, 256]}, batch=B)
-    t_setup, scorer = _clock(lambda: _TimedLstm(pred, table, np.asarray(table["flow"], np.float64), n))
-    C, Q = scorer.res.C, scorer.res.Q
-    rec = _measure(pred, table, scorer, list(range(C + Q)), passes, host_passes, rounds)
+    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table, np.asarray(table["flow"], np.float64)))
+    rec = _measure(pred, table, scorer, list(range(len(scorer.ps.names))), passes, host_passes, rounds)
     pred.eng.check_device_errors()
     rec.update(rows=n, windows=int(scorer.M), features=pipe.n_features, engine_batch=B, setup_s=t_setup)
     return rec

@@ -19,6 +19,7 @@ the same machine state:
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -32,11 +33,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from wellflow.data.features import FeaturePipeline, SeriesWindows, take, window_starts  # noqa: E402
+from wellflow.data.features import FeaturePipeline, take  # noqa: E402
 from wellflow.data.io import load_table  # noqa: E402
 from wellflow.data.schema import parse_schema  # noqa: E402
 from wellflow.models import registry  # noqa: E402
-from wellflow.ops.native import lib  # noqa: E402
+from wellflow.ops import native  # noqa: E402
 from wellflow.predict import Predictor  # noqa: E402
 from wellflow.utils.checkpoint import save_mdl  # noqa: E402
 
@@ -65,30 +66,24 @@ def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
     return Predictor.load(p, schema, device="cuda", precision="bf16", batch=batch)
 
 
-def mlp_host_score(pred, table, stages):
-    """Host assembly: the feature matrix built by numpy, widened to the engine's bf16 rows and
-    uploaded; then the same chunked forward as the device path."""
-    eng, B = pred.eng, pred.eng_batch
-    t, X = _clock(lambda: pred.pipe.features(table))
-    stages["host_stage_s"].append(t)
-
-    def dev():
-        Xd = eng.to_input_format(torch.from_numpy(X)).to(pred.device)
-        out = torch.empty(len(X), device=pred.device)
-        for c in range(0, len(X), B):
-            out[c : c + B].copy_(eng.forward(Xd[c : c + B]))
-        return np.asarray(pred.pipe.inverse_target(out.cpu().numpy()), np.float32)
-
-    t, y = _clock(dev)
-    stages["device_stage_s"].append(t)
-    return y
+@contextlib.contextmanager
+def host_assembly():
+    """``Predictor.predict_table`` on its host-assembly route (that of tables wider than the device
+    assembly takes): the feature matrix built by numpy and uploaded, then the same forward."""
+    keep, native.ASSEMBLE_MAX_F = native.ASSEMBLE_MAX_F, 0
+    try:
+        yield
+    finally:
+        native.ASSEMBLE_MAX_F = keep
 
 
-def mlp_device_score(pred, table, stages):
-    t, _ = _clock(lambda: pred.pipe.raw_columns(table))
+def mlp_score(pred, table, stages, host_stage):
+    """One ``predict_table``; ``host_stage`` (the label lookup / the feature matrix) is timed alone
+    first, because predict_table redoes it."""
+    t, _ = _clock(lambda: host_stage(table))
     stages["host_stage_s"].append(t)
     t, y = _clock(lambda: pred.predict_table(table))
-    stages["device_stage_s"].append(max(t - stages["host_stage_s"][-1], 0.0))  # predict_table redoes the lookup
+    stages["device_stage_s"].append(max(t - stages["host_stage_s"][-1], 0.0))
     stages["total_s"].append(t)
     return y
 
@@ -105,14 +100,14 @@ def bench_mlp(rows, rounds, tmp):
     pred = _predictor(tmp, "mlp", MLPRegressor(pipe.n_features, (256, 256)), pipe, schema)
     dev = {"host_stage_s": [], "device_stage_s": [], "total_s": []}
     host = {"host_stage_s": [], "device_stage_s": [], "total_s": []}
-    yd = mlp_device_score(pred, table, {k: [] for k in dev})  # warm-up of both paths (engine build, code objects)
-    yh = mlp_host_score(pred, table, {k: [] for k in host})
+    yd = mlp_score(pred, table, {k: [] for k in dev}, pipe.raw_columns)  # warm-up of both paths (engine, code objects)
+    with host_assembly():
+        yh = mlp_score(pred, table, {k: [] for k in host}, pipe.features)
     same = bool(np.array_equal(yd, yh))
     for _ in range(rounds):
-        mlp_device_score(pred, table, dev)
-        s = len(host["host_stage_s"])
-        mlp_host_score(pred, table, host)
-        host["total_s"].append(host["host_stage_s"][s] + host["device_stage_s"][s])
+        mlp_score(pred, table, dev, pipe.raw_columns)
+        with host_assembly():
+            mlp_score(pred, table, host, pipe.features)
     rec = {"rows": n, "features": pipe.n_features, "engine_batch": pred.eng_batch, "bit_identical": same}
     for name, st in (("device_assembly", dev), ("host_assembly", host)):
         rec[name] = {k: _median(v) for k, v in st.items()}
@@ -137,20 +132,8 @@ def bench_lstm(rounds, tmp):
                       job={"seq_len": T, "group_col": "well", "hidden": H, "mlp_hidden": [256, 256]}, batch=B)
 
     def host_score():
-        stable, ids, order = pred._sorted_series(table, n)
-        starts = np.asarray(window_starts(n, T, ids), np.int64)
-        rows = torch.from_numpy(pred.pipe.features(stable)).to(dev)
-        win = SeriesWindows(rows, torch.from_numpy(starts).to(dev), T)
-        out = torch.empty(len(starts), device=dev)
-        for a in range(0, len(starts), B):
-            m = min(B, len(starts) - a)
-            ids_d = torch.arange(a, a + B, device=dev).clamp_(max=a + m - 1)
-            out[a : a + m].copy_(pred.eng.forward_windows(win, ids_d)[:m])
-        full = np.full(n, np.nan, np.float32)
-        full[starts + T - 1] = pred.pipe.inverse_target(out.cpu().numpy())
-        res = np.empty(n, np.float32)
-        res[order] = full
-        return res
+        with host_assembly():
+            return pred.predict_table(table)
 
     yd = pred.predict_table(table)
     yh = host_score()
@@ -174,7 +157,7 @@ def bench_kernel(pipe, table, rounds, launches=20):
     mean, std = pipe.scale()
     codes_d, cont_d = torch.from_numpy(codes).to(dev), torch.from_numpy(cont).to(dev)
     spec = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (off, size, mean, std)]
-    C = lib()
+    C = native.lib()
     n, F = codes.shape[1], pipe.n_features
     out = {}
     for label, dt in (("bf16", torch.bfloat16), ("fp32", torch.float32)):
@@ -183,7 +166,7 @@ def bench_kernel(pipe, table, rounds, launches=20):
         dst = torch.empty((n, ld), dtype=dt, device=dev)
         a = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)  # a copy reads and writes: same total bytes
         b = torch.empty_like(a)
-        run_k = lambda: C.assemble_features(codes_d, cont_d, *spec, n, F, dst)  # noqa: E731  (the launch alone)
+        run_k = lambda: C.assemble_features(codes_d, cont_d, *spec, 0, n, F, dst, -1, None)  # noqa: E731  (the launch alone)
         run_c = lambda: b.copy_(a)  # noqa: E731
         tk, tc = [], []
         for fn in (run_k, run_c):
