@@ -72,6 +72,8 @@ void gemm(const at::Tensor& A, bool a_mn, int64_t lda, const at::Tensor& B, bool
           c10::optional<at::Tensor> mask, int64_t ldm, double mask_scale,
           c10::optional<at::Tensor> colsum, double alpha, double beta, int64_t act, bool atomic,
           double drop_p, int64_t seed, int64_t big_tile, c10::optional<at::Tensor> seed_dev) {
+  TORCH_CHECK(wf::dw_tile_valid(big_tile), "gemm: tile ", big_tile, " does not exist; valid ids are 0 (128x128), ",
+              "1 (256x128), 3 (256x192), 4 / 5 (256x192, 5- / 4-slot ring), 7 (best for N)");
   check_t(A, at::kBFloat16, "A");
   check_t(B, at::kBFloat16, "B");
   TORCH_CHECK(M > 0 && N > 0 && K > 0, "gemm: empty problem");
@@ -240,13 +242,9 @@ bool lstm_forward_persistent(const at::Tensor& XH, const at::Tensor& Wp, const a
                            "persistent LSTM forward");
 }
 
-void lstm_backward(const at::Tensor& WhhT, const at::Tensor& XH, const at::Tensor& Cst,
-                   const at::Tensor& S, const at::Tensor& DG, const at::Tensor& dcarry,
-                   const at::Tensor& dy, const at::Tensor& w_out, int64_t B, int64_t T, int64_t F,
-                   int64_t KX, int64_t H, int64_t variant, const c10::optional<at::Tensor>& sync) {
-  auto d = lstm_dims(B, T, F, KX, H);
-  d.bwd_variant = (int)variant;
-  check_lstm_state(XH, Cst, S, d);
+// Operands of the BPTT chain (lstm_backward, lstm_backward_dw) next to the forward state.
+void check_lstm_bwd(const at::Tensor& WhhT, const at::Tensor& DG, const at::Tensor& dcarry, const at::Tensor& dy,
+                    const at::Tensor& w_out, int64_t B, int64_t T, int64_t H) {
   check_t(WhhT, at::kBFloat16, "WhhT");
   check_extent(WhhT, H * 4 * H, "WhhT");
   check_t(DG, at::kBFloat16, "DG");
@@ -257,6 +255,16 @@ void lstm_backward(const at::Tensor& WhhT, const at::Tensor& XH, const at::Tenso
   check_extent(dy, B, "dy");
   check_t(w_out, at::kFloat, "w_out");
   check_extent(w_out, H, "w_out");
+}
+
+void lstm_backward(const at::Tensor& WhhT, const at::Tensor& XH, const at::Tensor& Cst,
+                   const at::Tensor& S, const at::Tensor& DG, const at::Tensor& dcarry,
+                   const at::Tensor& dy, const at::Tensor& w_out, int64_t B, int64_t T, int64_t F,
+                   int64_t KX, int64_t H, int64_t variant, const c10::optional<at::Tensor>& sync) {
+  auto d = lstm_dims(B, T, F, KX, H);
+  d.bwd_variant = (int)variant;
+  check_lstm_state(XH, Cst, S, d);
+  check_lstm_bwd(WhhT, DG, dcarry, dy, w_out, B, T, H);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(XH.device());
   auto s = cur_stream();
   if (sync.has_value()) {  // step T-1, then the persistent chain (tools/pb_time.py)
@@ -319,16 +327,7 @@ bool lstm_backward_dw(const at::Tensor& WhhT, const at::Tensor& XH, const at::Te
   auto d = lstm_dims(B, T, F, KX, H);
   d.bwd_variant = (int)variant;
   check_lstm_state(XH, Cst, S, d);
-  check_t(WhhT, at::kBFloat16, "WhhT");
-  check_extent(WhhT, H * 4 * H, "WhhT");
-  check_t(DG, at::kBFloat16, "DG");
-  check_extent(DG, T * B * 4 * H, "DG");
-  check_t(dcarry, at::kFloat, "dcarry");
-  check_extent(dcarry, (B + 15) / 16 * 16 * H, "dcarry");
-  check_t(dy, at::kFloat, "dy");
-  check_extent(dy, B, "dy");
-  check_t(w_out, at::kFloat, "w_out");
-  check_extent(w_out, H, "w_out");
+  check_lstm_bwd(WhhT, DG, dcarry, dy, w_out, B, T, H);
   check_t(gW, at::kFloat, "gW");
   const int64_t G = 4 * H, KA = KX + H;
   check_extent(gW, G * KA, "gW");
@@ -341,13 +340,7 @@ bool lstm_backward_dw(const at::Tensor& WhhT, const at::Tensor& XH, const at::Te
     e.outF = fp(gW);
     e.ldo = KA;
     e.atomic = 1;
-    // WELLFLOW_DW_BIG: 0 = 128x128 tile, 1 = 256x128 8-wave, 2 = 128x288 4-wave,
-    // 3 = 256x192 8-wave (tools/tune_lstm.py, B = 8192, split-K 32: 1.35 / 1.60 / 1.28 ms for
-    // 1 / 2 / 3), 4 / 5 = 256x192 with a 5- / 4-slot 32-deep ring, 6 = 256x192 with staggered
-    // wave groups, 7 (default) = 256x288 4-slot 32-deep ring (tools/dw_tiles.py: 1.107 ms vs
-    // 1.166 for 3, 1.149 for 4, 1.307 for 6); shapes a tile cannot take fall back to 256x128
-    static const int big = diag_env("WELLFLOW_DW_BIG", 7);
-    e.big_tile = big;
+    e.big_tile = wf::kDwBest;
     if (dw_slab.has_value()) {  // split-K partials plain-stored, one reduce (gemm.hip launch_dw_288w)
       check_t(*dw_slab, at::kFloat, "dw_slab");
       e.slab = fp(*dw_slab);

@@ -168,9 +168,19 @@ static void launch_cfg(const bf16_t* A, long lda, const bf16_t* B, long ldb, int
                        N, K, kchunk, e);
 }
 
-// Big-tile configuration for the MN x MN weight-gradient GEMMs (dW = dZ^T X over a huge
-// batch/time K): 256x128 tile, 8 waves, 3-stage glds ring (144 KiB): 87 FLOP per staged
-// byte instead of 64 for 128x128.
+// ---- MN x MN split-K weight-gradient tiles (kernels.h DwTile) -------------------------------
+// dW = dZ^T X over a huge batch/time K. For the LSTM (M = 4H = 2048, N = KA = 576) the dW loop's
+// LDS-DMA bytes per CU per step, not its MFMAs or the DMA latency, track its time across tiles
+// (256x128 1.33, 256x192 1.17, 256x288 1.11 ms), so the widest tile that divides N wins.
+// Retired experiments and their records:
+//   128x288, 4 waves (1.60 ms, one wave per SIMD cannot hide the fragment reads): profiles/r1_lstm_summary.md
+//   256x192, staggered wave groups: profiles/r3_summary.md
+//   256x288, 4 waves of 128x144: profiles/r5/notes.md
+//   256x288, global_load_lds instead of buffer_load ... lds: profiles/r6/diag/glds.txt
+//   256x288, DMA pieces between the MFMAs: profiles/r6/diag/dw_dma_interleaved.txt
+
+// 256x128, 8 waves, 3-stage glds ring (144 KiB): 87 FLOP per staged byte instead of 64 for
+// 128x128. Takes any N (the generic epilogue masks the last column tile).
 static void launch_dw_big(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
                           int ksplit, const GemmEpilogue& e, hipStream_t s) {
   constexpr int BM = 256, BN = 128;
@@ -181,11 +191,6 @@ static void launch_dw_big(const bf16_t* A, long lda, const bf16_t* B, long ldb, 
                      dim3(512), 0, s, A, lda, B, ldb, M, N, K, kchunk, e);
 }
 
-// LSTM weight gradient (M = 4H = 2048, N = KA = 576, K = T*B), alternative tile: 128x288,
-// 4 waves of 64x144, 3-stage ring (156 KiB). N = 2 x 288 exactly (the 256x128 tile wastes
-// half of its 5th column tile) and 16 x 2 = 32 tiles per K split = one XCD's 32 CUs. Measured
-// slower than the 256x128 8-wave tile (1.60 vs 1.33 ms at split-K 32: one wave per SIMD
-// cannot hide the fragment reads), so it is opt-in (WELLFLOW_DW_BIG=2).
 // Split-K weight-gradient kernel: MN x MN operands, full tiles only (M % BM == N % BN == 0,
 // host-checked), epilogue = fp32 atomic add of alpha * acc (nothing else, so the 144
 // accumulator registers stay in registers).
@@ -212,47 +217,32 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dw_kernel(const bf16_t* __r
         atomicAdd(out + (size_t)cc.row(i, r) * ldo + cc.col(j), alpha * acc[i][j][r]);
 }
 
-static void launch_dw_288(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-                          int ksplit, const GemmEpilogue& e, hipStream_t s) {
-  constexpr int BM = 128, BN = 288;
-  const int tiles = (M / BM) * (N / BN);
-  // equal 64-aligned K chunks (K % (64 * nsplit) == 0 is required: partial chunks would need
-  // the masked mainloop)
+// equal 64-aligned K chunks (K % (64 * nsplit) == 0 is required: partial chunks would need the
+// masked mainloop)
+static int equal_ksplit(int K, int ksplit) {
   int nsplit = ksplit;
   while (nsplit > 1 && K % (64 * nsplit) != 0) --nsplit;
-  const int kchunk = K / nsplit;
-  hipLaunchKernelGGL((gemm_dw_kernel<BM, BN, 3, 2, 2>), dim3(tiles * nsplit), dim3(256), 0, s, A, lda, B, ldb,
-                     N, kchunk, tiles, e.outF, e.ldo, e.alpha);
+  return nsplit;
 }
 
 // 256x192, 8 waves of 64x96, 2-stage ring (112 KiB): N = 576 = 3 x 192 exactly, and 22 % fewer
-// operand bytes per MFMA than 256x128 (rotation-swizzled 192-wide MN image).
+// operand bytes per MFMA than 256x128 (rotation-swizzled 192-wide MN image). s_setprio(1) around
+// each MFMA cluster (cdna_hip_programming.md §5.5 T5: hipcc then keeps the clusters between the
+// barriers): 1.24 -> 1.16 ms at B = 8192.
 static void launch_dw_192(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
                           int ksplit, const GemmEpilogue& e, hipStream_t s) {
   constexpr int BM = 256, BN = 192;
   const int tiles = (M / BM) * (N / BN);
-  int nsplit = ksplit;
-  while (nsplit > 1 && K % (64 * nsplit) != 0) --nsplit;
+  const int nsplit = equal_ksplit(K, ksplit);
   const int kchunk = K / nsplit;
-  // s_setprio(1) around each MFMA cluster (cdna_hip_programming.md §5.5 T5: hipcc then keeps
-  // the clusters between the barriers): 1.24 -> 1.16 ms at B = 8192 (WELLFLOW_DW_PRIO=0/2: off /
-  // static priority for waves 4-7, no gain)
-  constexpr int prio = 1;  // WELLFLOW_DW_PRIO=0/2 measured no gain (round 2): knob removed in round 5
-  if (prio == 1)
-    hipLaunchKernelGGL((gemm_dw_kernel<BM, BN, 2, 4, 2, 1>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B, ldb,
-                       N, kchunk, tiles, e.outF, e.ldo, e.alpha);
-  else if (prio == 2)
-    hipLaunchKernelGGL((gemm_dw_kernel<BM, BN, 2, 4, 2, 2>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B, ldb,
-                       N, kchunk, tiles, e.outF, e.ldo, e.alpha);
-  else
-    hipLaunchKernelGGL((gemm_dw_kernel<BM, BN, 2, 4, 2>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B, ldb,
-                       N, kchunk, tiles, e.outF, e.ldo, e.alpha);
+  hipLaunchKernelGGL((gemm_dw_kernel<BM, BN, 2, 4, 2, 1>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B, ldb,
+                     N, kchunk, tiles, e.outF, e.ldo, e.alpha);
 }
 
-// 256x192, 8 waves of 64x96, 32-deep half steps through an NSLOT-deep ring (gemm_core.h
-// gemm_mainloop_glds_h): the same tile as launch_dw_192 with its DMA issued NSLOT - 1 half
-// steps ahead instead of one 64-deep step
-template <int BM, int BN, int NSLOT, int WM, int WN, int PRIO, int BKD = 32, bool GL = false, int DG = 0>
+// The same contract as gemm_dw_kernel with BKD-deep steps through an NSLOT-deep ring
+// (gemm_core.h gemm_mainloop_glds_h), and the split's partial tile either added into `out` or,
+// given a slab, plain-stored for dw_slab_reduce_kernel.
+template <int BM, int BN, int NSLOT, int WM, int WN, int PRIO, int BKD = 32>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_dw_h_kernel(const bf16_t* __restrict__ A, long lda,
                                                         const bf16_t* __restrict__ B, long ldb, int N,
                                                         int kchunk, int tiles, float* __restrict__ out,
@@ -266,7 +256,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dw_h_kernel(const bf16_t* _
   const int split = L / tiles, t = L % tiles;
   const int m0 = (t / tiles_n) * BM, n0 = (t % tiles_n) * BN;
   f32x4 acc[C::TM][C::TN];
-  gemm_mainloop_glds_h<C, NSLOT, PRIO, BKD, GL, DG>(A, lda, B, ldb, split * kchunk, kchunk / BKD, m0, n0, smem, acc);
+  gemm_mainloop_glds_h<C, NSLOT, PRIO, BKD>(A, lda, B, ldb, split * kchunk, kchunk / BKD, m0, n0, smem, acc);
   const AccCoord<C> cc(m0, n0);
   if (slab != nullptr) {  // this split's partial tile, plain-stored (dw_slab_reduce_kernel adds the splits)
     float* o = slab + (size_t)split * slab_stride;
@@ -287,42 +277,16 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dw_h_kernel(const bf16_t* _
         atomicAdd(out + (size_t)cc.row(i, r) * ldo + cc.col(j), alpha * acc[i][j][r]);
 }
 
-// the same tile and 2-slot 64-deep ring as launch_dw_192, wave groups staggered by a barrier
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_dw_s_kernel(const bf16_t* __restrict__ A, long lda,
-                                                        const bf16_t* __restrict__ B, long ldb, int N,
-                                                        int kchunk, int tiles, float* __restrict__ out,
-                                                        long ldo, float alpha) {
-  using C = GemmCfg<BM, BN, MN_CONTIG, MN_CONTIG, WM, WN>;
-  __shared__ __attribute__((aligned(16))) char smem[2 * C::STAGE];
-  const int tiles_n = N / BN;
-  const int L = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = L / tiles, t = L % tiles;
-  const int m0 = (t / tiles_n) * BM, n0 = (t % tiles_n) * BN;
-  f32x4 acc[C::TM][C::TN];
-  gemm_mainloop_stag<C>(A, lda, B, ldb, split * kchunk, kchunk / 64, m0, n0, smem, acc);
-  const AccCoord<C> cc(m0, n0);
-#pragma unroll
-  for (int j = 0; j < C::TN; ++j)
-#pragma unroll
-    for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        atomicAdd(out + (size_t)cc.row(i, r) * ldo + cc.col(j), alpha * acc[i][j][r]);
-}
-
+// The 256x192 tile of launch_dw_192 through the half-step ring, its DMA issued NSLOT - 1 half
+// steps ahead instead of one 64-deep step (kDw256x192Ring5 / Ring4, A/B only)
 static void launch_dw_192h(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
                            int ksplit, int nslot, const GemmEpilogue& e, hipStream_t s) {
   constexpr int BM = 256, BN = 192;
   const int tiles = (M / BM) * (N / BN);
-  int nsplit = ksplit;
-  while (nsplit > 1 && K % (64 * nsplit) != 0) --nsplit;
+  const int nsplit = equal_ksplit(K, ksplit);
   const int kchunk = K / nsplit;
   const dim3 grid(tiles * nsplit);
-  if (nslot == 2)  // staggered wave groups (gemm_mainloop_stag)
-    hipLaunchKernelGGL((gemm_dw_s_kernel<BM, BN, 4, 2>), grid, dim3(512), 0, s, A, lda, B, ldb, N, kchunk, tiles,
-                       e.outF, e.ldo, e.alpha);
-  else if (nslot == 5)
+  if (nslot == 5)
     hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 5, 4, 2, 1>), grid, dim3(512), 0, s, A, lda, B, ldb, N, kchunk,
                        tiles, e.outF, e.ldo, e.alpha, nullptr, 0L);
   else
@@ -352,14 +316,11 @@ __global__ __launch_bounds__(256) void dw_slab_reduce_kernel(float* __restrict__
   reinterpret_cast<float4*>(out)[i] = a;
 }
 
-// 256x288, 8 waves of 64x144, 4-slot 32-deep ring (136 KiB; a 2-stage 64-deep ring spilled 61 VGPRs).
-// Round 5: 4 waves of 128x144 (one per SIMD, accumulators in AGPRs; 35 % fewer LDS fragment
-// reads) measured 1.18-1.25 vs 1.03 ms standalone (tools/dw_tiles.py, profiles/r5/notes.md): removed
-// (default: 1.107 vs 1.166 ms for 256x192 standalone, 1.150 vs 1.178 ms inside the bench step): N = 576 = 2 x 288, 24 % more
-// FLOP per staged byte than 256x192 (the dW loop's LDS-DMA bytes per CU per step, not its
-// MFMAs or the DMA latency, track its time across tiles: 256x128 1.33, 256x192 1.17 ms)
+// 256x288, 8 waves of 64x144, 4-slot 32-deep ring (136 KiB; a 2-stage 64-deep ring spilled 61
+// VGPRs): N = 576 = 2 x 288, 24 % more FLOP per staged byte than 256x192 (1.107 vs 1.166 ms
+// standalone, 1.150 vs 1.178 ms inside the bench step). s_setprio(1) around each MFMA cluster.
 static void launch_dw_288w(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-                           int ksplit, const GemmEpilogue& e, hipStream_t s, bool gl = false, int dg = 0) {
+                           int ksplit, const GemmEpilogue& e, hipStream_t s) {
   constexpr int BM = 256, BN = 288;
   const int tiles = (M / BM) * (N / BN);
   // one workgroup per CU: 16 tiles x split-K 16 on 256 CUs (tools/dw_tiles.py, B = 8192:
@@ -371,38 +332,14 @@ static void launch_dw_288w(const bf16_t* A, long lda, const bf16_t* B, long ldb,
     return n;
   }();
   if (ksplit * tiles > cus && cus / tiles >= 1) ksplit = cus / tiles;
-  int nsplit = ksplit;
-  while (nsplit > 1 && K % (64 * nsplit) != 0) --nsplit;
+  const int nsplit = equal_ksplit(K, ksplit);
   const int kchunk = K / nsplit;
   // split-K partials: fp32 atomics into the output (2048 x 576 x 16 splits = 75 MB of 64-B-segment
   // atomics at the tail of the kernel) or, given a slab, plain stores + one reduce
   const long mn = (long)M * N;
   const bool use_slab = e.slab != nullptr && e.ldo == N && nsplit > 1 && (long)nsplit * mn <= e.slab_cap && mn % 4 == 0;
-  // s_setprio 1 around each MFMA cluster (static priority for waves 4-7 measured slower, r4/lstm_dw_prio;
-  // the WELLFLOW_DW288_PRIO knob was removed in round 5)
-  constexpr int prio = 1;
-  if (dg == 1)  // tiles 9 / 10: diagnostics (wrong results), gemm_core.h gemm_mainloop_glds_h DG
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1, 32, false, 1>), dim3(tiles * nsplit), dim3(512), 0, s, A,
-                       lda, B, ldb, N, kchunk, tiles, e.outF, e.ldo, e.alpha, use_slab ? e.slab : nullptr,
-                       use_slab ? mn : 0L);
-  else if (dg == 2)
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1, 32, false, 2>), dim3(tiles * nsplit), dim3(512), 0, s, A,
-                       lda, B, ldb, N, kchunk, tiles, e.outF, e.ldo, e.alpha, use_slab ? e.slab : nullptr,
-                       use_slab ? mn : 0L);
-  else if (dg == 3)  // tile 11: DMA pieces between the MFMAs (gemm_core.h DG 3)
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1, 32, false, 3>), dim3(tiles * nsplit), dim3(512), 0, s, A,
-                       lda, B, ldb, N, kchunk, tiles, e.outF, e.ldo, e.alpha, use_slab ? e.slab : nullptr,
-                       use_slab ? mn : 0L);
-  else if (gl)  // tile 8 (A/B): the DMA by global_load_lds; measured slower (1.105 vs 1.050 ms, r6/diag/glds.txt)
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1, 32, true>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda,
-                       B, ldb, N, kchunk, tiles, e.outF, e.ldo, e.alpha, use_slab ? e.slab : nullptr,
-                       use_slab ? mn : 0L);
-  else if (prio == 3)
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 3, 32>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B,
-                       ldb, N, kchunk, tiles, e.outF, e.ldo, e.alpha, use_slab ? e.slab : nullptr, use_slab ? mn : 0L);
-  else
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1, 32>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B,
-                       ldb, N, kchunk, tiles, e.outF, e.ldo, e.alpha, use_slab ? e.slab : nullptr, use_slab ? mn : 0L);
+  hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1, 32>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B,
+                     ldb, N, kchunk, tiles, e.outF, e.ldo, e.alpha, use_slab ? e.slab : nullptr, use_slab ? mn : 0L);
   if (use_slab) {
     const long n4 = mn / 4;
     hipLaunchKernelGGL(dw_slab_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, e.outF,
@@ -412,34 +349,18 @@ static void launch_dw_288w(const bf16_t* A, long lda, const bf16_t* B, long ldb,
 
 void launch_gemm(const bf16_t* A, long lda, int a_mn, const bf16_t* B, long ldb, int b_mn, int M,
                  int N, int K, int ksplit, const GemmEpilogue& e, hipStream_t s, bool glds_ok) {
-  if (a_mn && b_mn && glds_ok && e.atomic && (e.big_tile >= 7 && e.big_tile <= 11) && M % 256 == 0 && K % 64 == 0) {
-    if (N % 288 == 0) {
-      launch_dw_288w(A, lda, B, ldb, M, N, K, ksplit < 1 ? 1 : ksplit, e, s, e.big_tile == 8,
-                     e.big_tile >= 9 ? e.big_tile - 8 : 0);
-      return;
-    }
-    if (N % 192 == 0) {  // e.g. H = 128 (KA = 192): the 256x192 tile
-      launch_dw_192(A, lda, B, ldb, M, N, K, ksplit < 1 ? 1 : ksplit, e, s);
-      return;
-    }
-  }
-  // 4 / 5: the 256x192 tile with the 5- / 4-slot half-step ring; 6: staggered wave groups
-  if (a_mn && b_mn && glds_ok && e.atomic && (e.big_tile >= 4 && e.big_tile <= 6) && M % 256 == 0 &&
-      N % 192 == 0 && K % 64 == 0) {
-    launch_dw_192h(A, lda, B, ldb, M, N, K, ksplit < 1 ? 1 : ksplit,
-                   e.big_tile == 4 ? 5 : (e.big_tile == 5 ? 4 : 2), e, s);
-    return;
-  }
-  if (a_mn && b_mn && glds_ok && e.atomic && e.big_tile == 2 && M % 128 == 0 && N % 288 == 0 && K % 64 == 0) {
-    launch_dw_288(A, lda, B, ldb, M, N, K, ksplit < 1 ? 1 : ksplit, e, s);
-    return;
-  }
-  if (a_mn && b_mn && glds_ok && e.atomic && e.big_tile == 3 && M % 256 == 0 && N % 192 == 0 && K % 64 == 0) {
-    launch_dw_192(A, lda, B, ldb, M, N, K, ksplit < 1 ? 1 : ksplit, e, s);
-    return;
-  }
-  if (a_mn && b_mn && glds_ok && e.atomic && e.big_tile && M % 256 == 0 && K % 64 == 0) {
-    launch_dw_big(A, lda, B, ldb, M, N, K, ksplit < 1 ? 1 : ksplit, e, s);
+  // the weight-gradient tiles: whole 256-row tiles of MN x MN operands, whole 64-deep K steps,
+  // the whole-tile over-read allowed by the host, atomic epilogue
+  if (a_mn && b_mn && glds_ok && e.atomic && e.big_tile != kDwGeneric && M % 256 == 0 && K % 64 == 0) {
+    const int ks = ksplit < 1 ? 1 : ksplit;
+    if (e.big_tile == kDwBest && N % 288 == 0)
+      launch_dw_288w(A, lda, B, ldb, M, N, K, ks, e, s);
+    else if ((e.big_tile == kDw256x192Ring5 || e.big_tile == kDw256x192Ring4) && N % 192 == 0)
+      launch_dw_192h(A, lda, B, ldb, M, N, K, ks, e.big_tile == kDw256x192Ring5 ? 5 : 4, e, s);
+    else if (e.big_tile != kDw256x128 && N % 192 == 0)  // e.g. H = 128 (KA = 192)
+      launch_dw_192(A, lda, B, ldb, M, N, K, ks, e, s);
+    else  // e.g. H = 256 (KA = 320)
+      launch_dw_big(A, lda, B, ldb, M, N, K, ks, e, s);
     return;
   }
   if (!a_mn && !b_mn)

@@ -255,84 +255,13 @@ struct GldsTile {
   }
 };
 
-// Same contract as gemm_mainloop but for FULL tiles only (m0+BM <= M, n0+BN <= N,
-// kbeg + 64*nk <= K): STAGES-deep LDS ring filled by glds, one barrier per K-step,
-// counted vmcnt so STAGES-2 tiles stay in flight across it (guide §5 "Pipelining across
-// barriers": raw s_barrier, never __syncthreads() while a glds is outstanding).
-template <class C, int STAGES>
-__device__ __forceinline__ void gemm_mainloop_glds(const bf16_t* __restrict__ A, long lda,
-                                                   const bf16_t* __restrict__ B, long ldb, int kbeg,
-                                                   int nk, int m0, int n0, char* smem,
-                                                   f32x4 (&acc)[C::TM][C::TN]) {
-  using TA = typename C::TA;
-  using TB = typename C::TB;
-  static_assert(STAGES >= 2 && STAGES <= 4, "2..4 stages");
-  constexpr int LA_ = C::LA_, LB_ = C::LB_;
-  using QA = GldsTile<C::BM, LA_, C::NT>;
-  using QB = GldsTile<C::BN, LB_, C::NT>;
-  constexpr int STAGE = QA::BYTES + QB::BYTES;
-  constexpr int LPT = QA::PER_WAVE + QB::PER_WAVE;  // glds per wave per K-tile
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wid / C::WN, wn = wid % C::WN;
-#pragma unroll
-  for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (nk <= 0) return;
-
-#pragma unroll
-  for (int s = 0; s < STAGES - 1; ++s) {
-    if (s < nk) {
-      char* st = smem + s * STAGE;
-      QA::issue(A, lda, m0, kbeg + s * 64, st, wid, lane);
-      QB::issue(B, ldb, n0, kbeg + s * 64, st + QA::BYTES, wid, lane);
-    }
-  }
-  for (int t = 0; t < nk; ++t) {
-    // tiles issued after t that may stay in flight: min(nk-1, t+STAGES-2) - t
-    const int ahead = min(nk - 1, t + STAGES - 2) - t;
-    if constexpr (STAGES >= 4) {
-      if (ahead >= 2) wait_vmcnt<2 * LPT>();
-      else if (ahead == 1) wait_vmcnt<LPT>();
-      else wait_vmcnt<0>();
-    } else if constexpr (STAGES == 3) {
-      if (ahead >= 1) wait_vmcnt<LPT>();
-      else wait_vmcnt<0>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    const int tn = t + STAGES - 1;
-    if (tn < nk) {  // refill the stage every wave finished reading in iteration t-1
-      char* st = smem + (tn % STAGES) * STAGE;
-      QA::issue(A, lda, m0, kbeg + tn * 64, st, wid, lane);
-      QB::issue(B, ldb, n0, kbeg + tn * 64, st + QA::BYTES, wid, lane);
-    }
-    const char* cur = smem + (t % STAGES) * STAGE;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 a[C::TM], b[C::TN];
-#pragma unroll
-      for (int i = 0; i < C::TM; ++i) a[i] = TA::frag(cur, wm * C::WTM + i * 16, kk, lane);
-#pragma unroll
-      for (int j = 0; j < C::TN; ++j) b[j] = TB::frag(cur + QA::BYTES, wn * C::WTN + j * 16, kk, lane);
-#pragma unroll
-      for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < C::TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  // leave LDS reusable by the caller's epilogue
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // ----------------------------------------------------------------------------------------
-// glds mainloop v2 — same pipeline/contract as gemm_mainloop_glds, built to keep the VALU
-// out of the MFMA stream (rocprofv3 showed VALU:MFMA = 5-7:1 in v1):
+// glds mainloop: acc += A[m0:m0+BM, kbeg:kbeg+64*nk] * B[n0:n0+BN, ...]^T for FULL tiles only
+// (m0+BM <= M, n0+BN <= N, kbeg + 64*nk <= K): STAGES-deep LDS ring filled by glds, one barrier
+// per K-step, counted vmcnt so STAGES-2 tiles stay in flight across it (guide §5 "Pipelining
+// across barriers": raw s_barrier, never __syncthreads() while a glds is outstanding). Built to
+// keep the VALU out of the MFMA stream (rocprofv3 showed VALU:MFMA = 5-7:1 with per-tile
+// address arithmetic):
 //  * every per-lane address is computed ONCE: glds sources are (scalar tile base) +
 //    (32-bit per-lane byte offset), the scalar base advancing by one K-step per tile;
 //  * fragment reads use per-lane LDS base offsets; the K-loop is unrolled by STAGES so
@@ -430,8 +359,8 @@ struct FragReader {
   }
 };
 
-// PRIO (A/B, cdna_hip_programming.md §5.5 T5): 1 = s_setprio(1) around each MFMA cluster;
-// 2 = the static form, waves 4-7 at priority 1 for the whole loop
+// PRIO 1 (cdna_hip_programming.md §5.5 T5): s_setprio(1) around each MFMA cluster (the 256x192
+// dW tile: 1.24 -> 1.16 ms at B = 8192; a static priority for waves 4-7 measured no gain, round 2).
 template <class C, int STAGES, int PRIO = 0>
 __device__ __forceinline__ void gemm_mainloop_glds2(const bf16_t* __restrict__ A, long lda,
                                                     const bf16_t* __restrict__ B, long ldb, int kbeg,
@@ -511,9 +440,6 @@ __device__ __forceinline__ void gemm_mainloop_glds2(const bf16_t* __restrict__ A
     });
   };
 
-  if constexpr (PRIO == 2) {
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-  }
   int t = 0;
   for (; t + STAGES <= nk; t += STAGES)
     static_for<0, STAGES>([&](auto uc) { body(t + decltype(uc)::value, uc); });
@@ -529,10 +455,11 @@ __device__ __forceinline__ void gemm_mainloop_glds2(const bf16_t* __restrict__ A
 // LDS ring. With 64-deep steps the 256x192 tile fits only 2 stages in 160 KiB, so each step's
 // LDS-DMA had exactly one step of MFMA work (~1.5k cycles per SIMD) to land and the
 // vmcnt(0) before every barrier exposed the rest of its latency (PMC: 28 % wave-wait, 54 % MFMA
-// busy). 32-deep slots of the same tile (28 KiB) fit 5 deep: a piece is issued NSLOT - 1 half
-// steps ahead of its use. Pieces that do not split evenly over the waves (the 192-wide image
-// is 12 pieces per half step) go to the low waves, and each wave counts its own in vmcnt.
-template <int R, int L, int NT, int BKD, bool GL = false>
+// busy); the 256x288 tile spilled with them. 32-deep slots fit 5 deep for 256x192 (28 KiB) and
+// 4 deep for 256x288 (34 KiB): a piece is issued NSLOT - 1 half steps ahead of its use. Pieces
+// that do not split evenly over the waves (the 192- and 288-wide images are 12 and 18 pieces per
+// half step) go to the low waves, and each wave counts its own in vmcnt.
+template <int R, int L, int NT, int BKD>
 struct GldsOpH {
   static_assert(L == MN_CONTIG, "half-step ring: MN-contiguous operands only");
   static constexpr int BYTES = R * BKD * 2;
@@ -544,10 +471,10 @@ struct GldsOpH {
   using SW = MnSwz<R>;
   // buffer-resource form (buffer_load ... lds): a 32-bit per-lane voffset and a scalar step
   // offset, no 64-bit per-lane addresses (global_load_lds with 64-bit VGPR addresses spilled
-  // the 288-wide tile's kernel). The workgroup's whole K range is < 2 GiB from its origin.
+  // the 288-wide tile's kernel, and its saddr form measured 5 % slower: profiles/r6/diag/glds.txt).
+  // The workgroup's whole K range is < 2 GiB from its origin.
   unsigned src[MAXPW];
   __amdgpu_buffer_rsrc_t rsrc;
-  const char* base;  // GL: the same origin as a plain pointer
   int kstep_bytes;
 
   __device__ __forceinline__ void init(const bf16_t* p, long ld, int row0, int kbeg, int wid, int lane) {
@@ -560,56 +487,34 @@ struct GldsOpH {
     }
     rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p + (size_t)kbeg * ld + row0), 0, 0x7FFFFFFF,
                                              0x00020000);
-    base = reinterpret_cast<const char*>(p + (size_t)kbeg * ld + row0);
     kstep_bytes = (int)(BKD * ld * 2);
-  }
-  // piece i of this wave alone (DG 3: pieces placed between the MFMAs)
-  __device__ __forceinline__ void issue1(int i, int step, char* lds_tile, int wid) const {
-    if (i + 1 < MAXPW || REM == 0 || wid < REM)  // wave-uniform
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(lds_tile + (i * NW + wid) * 1024), 16, (int)src[i],
-                                               step * kstep_bytes, 0, 0);
   }
   __device__ __forceinline__ void issue(int step, char* lds_tile, int wid) const {
     const int so = step * kstep_bytes;
 #pragma unroll
     for (int i = 0; i < MAXPW; ++i) {
-      if (i + 1 < MAXPW || REM == 0 || wid < REM) {  // wave-uniform
-        if constexpr (GL) {
-          // global_load_lds (round 6, tile 8 A/B) in its saddr form: the uniform base + step in
-          // SGPRs, the 32-bit lane offset in a VGPR (the builtin made 64-bit per-lane addresses
-          // and spilled). Tried because the probe charged the MUBUF form ~2x its issue time;
-          // the dW GEMM measured 5 % SLOWER with it (profiles/r6/diag/glds.txt). Inline asm: M0
-          // through its constraint, one wait state after the M0 write; the counted vmcnt waits
-          // of the ring cover it like the builtin.
-          const char* b = base + so;
-          const unsigned la = (unsigned)(uintptr_t)((lds_void*)(lds_tile + (i * NW + wid) * 1024));
-          asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(src[i]), "s"(b),
-                       "{m0}"(__builtin_amdgcn_readfirstlane(la))
-                       : "memory");
-        } else
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(lds_tile + (i * NW + wid) * 1024), 16, (int)src[i],
-                                                   so, 0, 0);
-      }
+      if (i + 1 < MAXPW || REM == 0 || wid < REM)  // wave-uniform
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(lds_tile + (i * NW + wid) * 1024), 16, (int)src[i],
+                                                 so, 0, 0);
     }
   }
 };
 
 // BKD = 64 with NSLOT = 2: the plain 2-stage ring of gemm_mainloop_glds2, for tiles whose
-// pieces do not split evenly over the waves (the 288-wide image: 36 pieces per 64-deep step)
-// DG (diagnostics, tools/dw_tiles.py tiles 9 / 10; results wrong): 1 = the ring's DMA for every
-// other half step only, 2 = no fragment reads and no MFMAs (the DMA + barrier floor).
-// DG 3 (tile 11, results exact): the half step's DMA pieces issued AFTER its fragment reads, one
-// between every few MFMAs — a piece costs its wave ~60 issue cycles among bare MFMAs but 100-185
-// in a phase of fragment reads (MI355X_MICROARCH.md, LDS-DMA piece issue cost)
-template <class C, int NSLOT, int PRIO = 0, int BKD = 32, bool GL = false, int DG = 0>
+// pieces do not split evenly over the waves (the 288-wide image: 36 pieces per 64-deep step).
+// PRIO 1: s_setprio(1) around each MFMA cluster (a static priority for the second-dispatched
+// waves measured slower: profiles/r4/lstm_dw_prio). The ring's DMA + barriers alone take 0.72 ms
+// (profiles/r6/diag/dw_dma_floor.txt); DMA pieces issued between the MFMAs instead of before
+// them gained 1 % (profiles/r6/diag/dw_dma_interleaved.txt).
+template <class C, int NSLOT, int PRIO = 0, int BKD = 32>
 __device__ __forceinline__ void gemm_mainloop_glds_h(const bf16_t* __restrict__ A, long lda,
                                                      const bf16_t* __restrict__ B, long ldb, int kbeg,
                                                      int nh, int m0, int n0, char* smem,
                                                      f32x4 (&acc)[C::TM][C::TN]) {
   static_assert(BKD == 32 || BKD == 64, "32- or 64-deep steps");
   static_assert(NSLOT >= 2 && NSLOT <= 6, "2..6 slots");
-  using OA = GldsOpH<C::BM, C::LA_, C::NT, BKD, GL>;
-  using OB = GldsOpH<C::BN, C::LB_, C::NT, BKD, GL>;
+  using OA = GldsOpH<C::BM, C::LA_, C::NT, BKD>;
+  using OB = GldsOpH<C::BN, C::LB_, C::NT, BKD>;
   static_assert(OA::REM == 0 || OB::REM == 0, "at most one operand with an uneven piece split");
   constexpr int STAGE = OA::BYTES + OB::BYTES;
   constexpr int LHI = OA::MAXPW + OB::MAXPW;                       // pieces per half step, low waves
@@ -624,10 +529,6 @@ __device__ __forceinline__ void gemm_mainloop_glds_h(const bf16_t* __restrict__ 
 #pragma unroll
     for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (nh <= 0) return;
-  // PRIO 3: static s_setprio 1 for the second-dispatched half of the waves (no per-cluster flips)
-  if constexpr (PRIO == 3) {
-    if (wid >= C::NT / 128) __builtin_amdgcn_s_setprio(1);
-  }
   OA oa;
   OB ob;
   oa.init(A, lda, m0, kbeg, wid, lane);
@@ -661,46 +562,17 @@ __device__ __forceinline__ void gemm_mainloop_glds_h(const bf16_t* __restrict__ 
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     const int tn = tt + NSLOT - 1;
-    if (DG != 3 && tn < nh && (DG != 1 || (tn & 1) == 0)) {
+    if (tn < nh) {
       constexpr int sn = (u + NSLOT - 1) % NSLOT;
       oa.issue(tn, smem + sn * STAGE, wid);
       ob.issue(tn, smem + sn * STAGE + OA::BYTES, wid);
     }
-    if constexpr (DG == 2) return;
     // slot origin as an opaque per-step value: with u * STAGE folded into every fragment
     // address (beyond the 16-bit ds offset field) the compiler hoisted one address register
     // per (slot, fragment) out of the loop, and the 288-wide tile spilled them
     int so = u * STAGE;
     asm volatile("" : "+v"(so));
     const char* sl = smem + so;
-    if constexpr (DG == 3) {
-      static_assert(BKD == 32, "DG 3: one fragment set per half step");
-      constexpr int NP = OA::MAXPW + OB::MAXPW;             // this wave's pieces (the last maybe none)
-      constexpr int NM = C::TM * C::TN, GAP = NM / (NP + 1);  // MFMAs between pieces
-      constexpr int sn = (u + NSLOT - 1) % NSLOT;
-      const bool more = tn < nh;
-      bf16x8 a[C::TM], b[C::TN];
-#pragma unroll
-      for (int i = 0; i < C::TM; ++i) a[i] = fa.template frag<0, 0>(sl, i);
-#pragma unroll
-      for (int j = 0; j < C::TN; ++j) b[j] = fbr.template frag<0, OA::BYTES>(sl, j);
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(1);
-      static_for<0, NM>([&](auto mc) {
-        constexpr int m = decltype(mc)::value, i = m / C::TN, j = m % C::TN;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-        if constexpr ((m + 1) % GAP == 0 && (m + 1) / GAP <= NP) {
-          constexpr int p = (m + 1) / GAP - 1;
-          __builtin_amdgcn_sched_barrier(0);
-          if (more) {
-            if constexpr (p < OA::MAXPW) oa.issue1(p, tn, smem + sn * STAGE, wid);
-            else ob.issue1(p - OA::MAXPW, tn, smem + sn * STAGE + OA::BYTES, wid);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      });
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(0);
-      return;
-    }
     static_for<0, BKD / 32>([&](auto kc) {
       constexpr int KK = decltype(kc)::value;
       bf16x8 a[C::TM], b[C::TN];
@@ -725,104 +597,6 @@ __device__ __forceinline__ void gemm_mainloop_glds_h(const bf16_t* __restrict__ 
   });
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-}
-
-// ----------------------------------------------------------------------------------------
-// Staggered wave groups (cdna_hip_programming.md §5 8-phase template, "if (wr == 1)
-// s_barrier"): same tile, 2-slot 64-deep ring and operand images as gemm_mainloop_glds2, but
-// every 32-deep phase is {fragment reads ; barrier ; MFMAs ; barrier} and waves 4-7 (the
-// second wave on each SIMD: waves go to SIMDs cyclically) run one barrier behind waves 0-3. In
-// every barrier interval one wave of a SIMD issues MFMAs while the other issues and waits for
-// its fragment reads; with one barrier per step both waves read, then both multiply (the
-// ring's DMA wait was not the limiter: the 5-slot half-step ring measured the same, 1.166 ms).
-// Barriers b = 0, 1, .. (after the prologue's): group A reads step t's phase 0 in interval 4t,
-// group B in 4t + 1, and so on. DMA(t + 1) into the slot of step t - 1 goes out after bar(4t),
-// when every read of that slot has retired (each wave's lgkmcnt wait precedes its MFMAs), and
-// every wave waits for its own pieces before bar(4t + 3), which precedes group A's first read
-// of step t + 1 (group A: its 4th barrier of step t, group B: its 3rd).
-template <class C, int PRIO = 1>
-__device__ __forceinline__ void gemm_mainloop_stag(const bf16_t* __restrict__ A, long lda,
-                                                   const bf16_t* __restrict__ B, long ldb, int kbeg,
-                                                   int nk, int m0, int n0, char* smem,
-                                                   f32x4 (&acc)[C::TM][C::TN]) {
-  static_assert(C::NT == 512, "two wave groups of 4 (one wave per SIMD each)");
-  using OA = GldsOperand<C::BM, C::LA_, C::NT>;
-  using OB = GldsOperand<C::BN, C::LB_, C::NT>;
-  constexpr int STAGE = OA::TILE_BYTES + OB::TILE_BYTES;
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wid / C::WN, wn = wid % C::WN;
-  const bool grp_b = wid >= 4;
-#pragma unroll
-  for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (nk <= 0) return;
-  OA oa;
-  OB ob;
-  oa.init(A, lda, m0, kbeg, wid, lane);
-  ob.init(B, ldb, n0, kbeg, wid, lane);
-  FragReader<C::BM, C::LA_, C::WTM> fa;
-  FragReader<C::BN, C::LB_, C::WTN> fbr;
-  fa.init(wm * C::WTM, lane);
-  fbr.init(wn * C::WTN, lane);
-  auto bar = [] {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  oa.issue(0, smem, wid);
-  ob.issue(0, smem + OA::TILE_BYTES, wid);
-  wait_vmcnt<0>();
-  bar();
-  if (grp_b) bar();  // group B runs one barrier behind
-
-  auto body = [&](int tt, auto uc) {
-    constexpr int u = decltype(uc)::value;  // == tt & 1
-    const bool more = tt + 1 < nk;
-    if (grp_b && more) {  // B: right after bar(4t), its last barrier of step t - 1
-      oa.issue(tt + 1, smem + (u ^ 1) * STAGE, wid);
-      ob.issue(tt + 1, smem + (u ^ 1) * STAGE + OA::TILE_BYTES, wid);
-    }
-    static_for<0, 2>([&](auto kc) {
-      constexpr int KK = decltype(kc)::value;
-      bf16x8 a[C::TM], b[C::TN];
-#pragma unroll
-      for (int i = 0; i < C::TM; ++i) a[i] = fa.template frag<KK, u * STAGE>(smem, i);
-#pragma unroll
-      for (int j = 0; j < C::TN; ++j) b[j] = fbr.template frag<KK, u * STAGE + OA::TILE_BYTES>(smem, j);
-      if constexpr (KK == 1) {
-        if (grp_b) wait_vmcnt<0>();  // B: before its 3rd barrier of the step = bar(4t + 3)
-      }
-      bar();
-      if constexpr (KK == 0) {
-        if (!grp_b && more) {  // A: right after bar(4t)
-          oa.issue(tt + 1, smem + (u ^ 1) * STAGE, wid);
-          ob.issue(tt + 1, smem + (u ^ 1) * STAGE + OA::TILE_BYTES, wid);
-        }
-      }
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < C::TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(0);
-      if constexpr (KK == 1) {
-        if (!grp_b) wait_vmcnt<0>();  // A: before its 4th barrier of the step = bar(4t + 3)
-      }
-      bar();
-    });
-  };
-  int t = 0;
-  for (; t + 2 <= nk; t += 2) {
-    body(t, std::integral_constant<int, 0>{});
-    body(t + 1, std::integral_constant<int, 1>{});
-  }
-  if (t < nk) body(t, std::integral_constant<int, 0>{});
-  if (!grp_b) bar();  // the barrier counts of the two groups meet again
 }
 
 // Output coordinates of accumulator element acc[i][j][r] (16x16 C/D map: col = lane&15,

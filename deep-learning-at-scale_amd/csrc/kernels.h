@@ -8,6 +8,22 @@ namespace wf {
 
 typedef unsigned short bf16_t;
 
+// Tile of the MN x MN split-K weight-gradient GEMM (both operands MN-contiguous, atomic
+// epilogue). The numbers are the ids tools, tests and logs use. A problem a tile cannot take
+// (M % 256, K % 64, N divisibility, whole-tile over-read not allowed) runs the generic kernels.
+enum DwTile : int {
+  kDwGeneric = 0,       // the 128x128 kernels of every other GEMM
+  kDw256x128 = 1,       // 8 waves, 3-stage 64-deep ring
+  kDw256x192 = 3,       // 8 waves, 2-stage 64-deep ring, N % 192 == 0; else 256x128
+  kDw256x192Ring5 = 4,  // A/B of the ring depth: 3 through a 5-slot 32-deep half-step ring
+  kDw256x192Ring4 = 5,  // and through a 4-slot one (profiles/r3_summary.md: the same time as 3)
+  kDwBest = 7,          // 256x288 half-step ring if N % 288 == 0, else 256x192 if N % 192 == 0, else 256x128
+};
+inline bool dw_tile_valid(long t) {
+  return t == kDwGeneric || t == kDw256x128 || t == kDw256x192 || t == kDw256x192Ring5 || t == kDw256x192Ring4 ||
+         t == kDwBest;
+}
+
 struct GemmEpilogue {
   float* outF = nullptr;         // fp32 output (also the beta / atomic target)
   bf16_t* outH = nullptr;        // bf16 output
@@ -24,7 +40,7 @@ struct GemmEpilogue {
   unsigned long long seed = 0;
   const long long* seed_dev = nullptr;  // optional device step counter mixed into the seed (graph replays)
   int stage_ok = 0;              // host-verified: bf16 output/mask tiles may go through LDS
-  int big_tile = 0;              // MN x MN split-K weight gradient: 1 = 256x128 8-wave tile, 2 = 128x288
+  int big_tile = kDwGeneric;     // DwTile of an MN x MN split-K weight gradient
   float* slab = nullptr;         // split-K partial slab (256x288 dW tile, ldo == N): plain stores of
   long slab_cap = 0;             // each split's tile, then one reduce adds the splits into outF
 };

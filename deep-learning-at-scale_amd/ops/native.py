@@ -162,7 +162,10 @@ def gemm(A, B, M, N, K, *, a_mn=False, lda=None, b_mn=False, ldb=None, outF=None
     """out = act(alpha * A(M,K) B(N,K)^T + beta*out + bias) (* mask), on MFMA.
 
     ``a_mn``/``b_mn`` select the MN-contiguous layout (X(r,k) = p[k*ld + r]).
-    ``tile`` (MN x MN split-K atomic only): 1 = 256x128 8-wave tile, 2 = 128x288, 3 = 256x192.
+    ``tile`` (MN x MN split-K atomic only; csrc/kernels.h DwTile): 0 = the generic 128x128
+    kernels, 1 = 256x128, 3 = 256x192 (N % 192 == 0, else 256x128), 4 / 5 = 3 through a 5- /
+    4-slot half-step ring (A/B), 7 = the best for N (256x288, else 256x192, else 256x128). Any
+    other id raises; a shape the tile cannot take runs as 0.
     ``seed_dev`` (int64 GPU tensor): a device step counter mixed into the dropout seed.
     """
     if lda is None:

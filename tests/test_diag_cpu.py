@@ -140,7 +140,7 @@ def test_native_env_knobs_are_documented():
     assert prod == documented_prod, (sorted(prod), sorted(documented_prod))
     assert diag <= documented_diag, sorted(diag - documented_diag)
     for gone in ("WELLFLOW_CNN_PRIO", "WELLFLOW_DW_PRIO", "WELLFLOW_DW288_PRIO", "WELLFLOW_STEP_PRIO",
-                 "WELLFLOW_DW2F_PRIO", "WELLFLOW_DW2F_PF"):
+                 "WELLFLOW_DW2F_PRIO", "WELLFLOW_DW2F_PF", "WELLFLOW_DW_BIG"):
         assert gone not in prod | diag, gone
 
 

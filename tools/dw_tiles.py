@@ -1,14 +1,10 @@
 """A/B of the LSTM weight-gradient tiles on the bench shape (M = 4H = 2048, N = KA = 576,
 K = T*B = 524288, MN x MN operands, split-K fp32 atomics): time per call, interleaved over
-rounds, and max |diff| against the default tile (3 = 256x192 64-deep 2-stage).
+rounds, and max |diff| against tile 3 (256x192, 64-deep 2-stage ring).
 
-    python tools/dw_tiles.py [tiles ...]      (default: 1 2 3; 4 / 5 = 256x192 with the 5- / 4-slot
-                                              32-deep half-step ring; 7 = the production 256x288,
-                                              8 = 256x288 with global_load_lds instead of MUBUF
-                                              LDS-DMA; 9 / 10 = diagnostics of 7, results wrong:
-                                              DMA every other half step / DMA + barriers only, no
-                                              fragment reads or MFMAs; 11 = 7 with the DMA pieces
-                                              between the MFMAs; DW_KS=16,32 picks the
+    python tools/dw_tiles.py [tiles ...]      (default: 1 3 7 = 256x128, 256x192, the production
+                                              256x288; 4 / 5 = 256x192 with the 5- / 4-slot
+                                              32-deep half-step ring; DW_KS=16,32 picks the
                                               split-K depths)
 """
 import sys
@@ -19,7 +15,7 @@ sys.path.insert(0, ".")
 from wellflow.ops.native import gemm  # noqa: E402
 
 M, N, K, KA = 2048, 576, 64 * 8192, 640
-tiles = [int(a) for a in sys.argv[1:]] or [1, 2, 3]
+tiles = [int(a) for a in sys.argv[1:]] or [1, 3, 7]
 torch.manual_seed(0)
 dG = (torch.randn(K, M, device="cuda") * 0.1).to(torch.bfloat16)
 XH = torch.randn(K, KA, device="cuda").to(torch.bfloat16)

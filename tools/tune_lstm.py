@@ -32,7 +32,7 @@ def main():
     ap.add_argument("--fwd", default="0,1,2")
     ap.add_argument("--bwd", default="0,1,2,3")
     ap.add_argument("--ksplit", default="8,16,32,64")
-    ap.add_argument("--tiles", default="1,2", help="dW GEMM tiles (1: 256x128, 2: 128x288)")
+    ap.add_argument("--tiles", default="1,3,7", help="dW GEMM tiles (1: 256x128, 3: 256x192, 7: best for N)")
     a = ap.parse_args()
     B, T, F, H = a.batch, 64, 16, 512
     eng = NativeLSTM(F, H, T, B)
