@@ -961,13 +961,17 @@ void transpose_cast_bf16(const at::Tensor& src, int64_t lds, int64_t rows, int64
 // the MLP input format) or fp32 (ld = F, the LSTM row table). cat_off / cat_size int32 [C], mean /
 // std fp32 [Q] (device); C = 0 or Q = 0: pass None. With perm_col in [0, C + Q) (categorical columns
 // first; else -1 and perm None) that source column is read through `perm` (int32 [N], indices into
-// all Ntot rows; the kernel clamps them): the permutation-importance pass.
+// all Ntot rows; the kernel clamps them): the permutation-importance pass. With const_col in
+// [0, C + Q) (else -1 and const_value None; not together with perm) that source column is the
+// CONSTANT const_value[0] instead, a one-element device tensor: an int32 label code for a
+// categorical column, an fp32 raw value for a continuous one: the response-curve pass.
 constexpr int64_t kAssembleMaxF = 512;
 
 void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
                        c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
                        c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t row0, int64_t N,
-                       int64_t F, const at::Tensor& out, int64_t perm_col, c10::optional<at::Tensor> perm) {
+                       int64_t F, const at::Tensor& out, int64_t perm_col, c10::optional<at::Tensor> perm,
+                       int64_t const_col, c10::optional<at::Tensor> const_value) {
   const bool has_c = codes.has_value() && codes->defined() && codes->numel() > 0;
   const bool has_q = cont.has_value() && cont->defined() && cont->numel() > 0;
   int64_t Ntot = -1;
@@ -1022,6 +1026,21 @@ void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor
                            : static_cast<const void*>(xp + (perm_col - C) * Ntot);
     pm.n = Ntot;
   }
+  const bool has_k = const_value.has_value() && const_value->defined();
+  TORCH_CHECK(has_k == (const_col >= 0), "assemble_features: const_col and const_value go together");
+  if (has_k) {
+    TORCH_CHECK(!has_p, "assemble_features: one source column is permuted or constant, not both (perm and const_col)");
+    TORCH_CHECK(const_col < C + Q, "assemble_features: const_col ", const_col, " outside 0 .. ", C + Q - 1);
+    TORCH_CHECK(const_value->is_cuda() && const_value->device() == out.device() && const_value->is_contiguous() &&
+                    const_value->numel() == 1,
+                "assemble_features: const_value must be a contiguous one-element tensor on the table's device");
+    const auto want = const_col < C ? at::kInt : at::kFloat;
+    TORCH_CHECK(const_value->scalar_type() == want, "assemble_features: const_value must be ",
+                const_col < C ? "int32 (a label code: a categorical column)" : "float32 (a raw value: a continuous column)");
+    pm.src = (int)const_col;
+    pm.broadcast = true;
+    pm.value = const_value->data_ptr();
+  }
   if (cp != nullptr) cp += row0;
   if (xp != nullptr) xp += row0;
   const bool ok = bf ? wf::launch_assemble_features_bf16(cp, xp, off, size, mu, sd, N, (int)C, (int)Q, (int)F, (int)ld,
@@ -1052,6 +1071,47 @@ void err_sums(const at::Tensor& pred, const at::Tensor& y, double y_scale, doubl
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(pred.device());
   wf::launch_err_sums(pred.data_ptr<float>(), y.data_ptr<float>(), pred.numel(), y_scale, y_shift,
                       out.data_ptr<double>() + 2 * slot, scratch.data_ptr<double>(), cur_stream());
+}
+
+// Grouped prediction sums (score.hip): out[slot][g] = {n_g, sum v, sum v^2}, v = pred * y_scale +
+// y_shift in fp64, from the host-built plan of ops/native.py GroupPlan: order int32 [M], pieces
+// int32 [2][P] (row 0 the first position of a piece in `order`, row 1 its length), group_pieces
+// int32 [G + 1], scratch fp64 [>= 3 P]. out fp64 [S][G][3]. Stream-ordered; nothing is read back.
+void group_sums(const at::Tensor& pred, const at::Tensor& order, const at::Tensor& pieces,
+                const at::Tensor& group_pieces, double y_scale, double y_shift, const at::Tensor& out, int64_t slot,
+                const at::Tensor& scratch) {
+  TORCH_CHECK(pred.defined() && pred.is_cuda() && pred.scalar_type() == at::kFloat && pred.is_contiguous() &&
+                  pred.dim() == 1,
+              "group_sums: pred must be a contiguous fp32 GPU vector");
+  const int64_t M = pred.numel();
+  TORCH_CHECK(M >= 1 && M <= INT32_MAX, "group_sums: ", M, " predictions (need 1 .. 2^31 - 1)");
+  for (const at::Tensor* t : {&order, &pieces, &group_pieces}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                "group_sums: order / pieces / group_pieces must be contiguous int32 GPU tensors");
+  }
+  TORCH_CHECK(order.dim() == 1 && order.numel() == M, "group_sums: the plan orders ", order.numel(), " predictions, pred holds ",
+              M);
+  TORCH_CHECK(pieces.dim() == 2 && pieces.size(0) == 2 && pieces.size(1) >= 1, "group_sums: pieces must be int32 [2][P]");
+  const int64_t P = pieces.size(1);
+  TORCH_CHECK(group_pieces.dim() == 1 && group_pieces.numel() >= 2, "group_sums: group_pieces must be int32 [G + 1]");
+  const int64_t G = group_pieces.numel() - 1;
+  TORCH_CHECK(G <= wf::kGroupSumsMaxGroups, "group_sums: ", G, " groups (at most ", wf::kGroupSumsMaxGroups, ")");
+  TORCH_CHECK(P <= M + G, "group_sums: ", P, " pieces for ", M, " predictions in ", G, " groups");
+  check_t(out, at::kDouble, "out");
+  check_t(scratch, at::kDouble, "scratch");
+  TORCH_CHECK(out.is_contiguous() && out.dim() == 3 && out.size(1) == G && out.size(2) == 3,
+              "group_sums: out must be contiguous fp64 [S][", G, "][3]");
+  TORCH_CHECK(slot >= 0 && slot < out.size(0), "group_sums: slot ", slot, " outside 0 .. ", out.size(0) - 1);
+  check_extent(scratch, 3 * P, "scratch");
+  for (const at::Tensor* t : {&order, &pieces, &group_pieces, &out, &scratch}) {
+    TORCH_CHECK(t->device() == pred.device(), "group_sums: tensors on different devices");
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(pred.device());
+  const bool ok = wf::launch_group_sums(pred.data_ptr<float>(), order.data_ptr<int>(), pieces.data_ptr<int>(),
+                                        pieces.data_ptr<int>() + P, group_pieces.data_ptr<int>(), M, (int)P, (int)G,
+                                        y_scale, y_shift, out.data_ptr<double>() + slot * G * 3,
+                                        scratch.data_ptr<double>(), cur_stream());
+  TORCH_CHECK(ok, "group_sums: the launcher refused the shape");
 }
 
 void im2col1d(const at::Tensor& x, int64_t B, int64_t L, int64_t Cin, int64_t ksz, int64_t Kp,
@@ -1369,8 +1429,12 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(gather_rows);
   WF_DEF(transpose_cast_bf16);
   WF_DEF(im2col1d);
-  WF_DEF(assemble_features);
+  // const_col / const_value are optional (and keywords): the twelve-argument call is the launch it was
+  m.def("assemble_features", &Checked<&assemble_features>::call, py::arg("codes"), py::arg("cont"), py::arg("cat_off"),
+        py::arg("cat_size"), py::arg("mean"), py::arg("std"), py::arg("row0"), py::arg("N"), py::arg("F"), py::arg("out"),
+        py::arg("perm_col"), py::arg("perm"), py::arg("const_col") = -1, py::arg("const_value") = py::none());
   WF_DEF(err_sums);
+  WF_DEF(group_sums);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
   m.def("cnn_fused_ok", &cnn_fused_ok);

@@ -41,6 +41,15 @@
 // out-of-bounds read. The wave index is the source column, so the branch is wave-uniform: one
 // wave per tile gathers (64 4-B reads, a 32-B sector each), every other column is read as
 // before, coalesced and once. perm_src = -1: no column matches, the launch is the plain one.
+//
+// One constant source (response curves, wellflow/response.py). With const_src in [0, C + Q) every
+// output row takes THAT column's value from the one-element device array const_val (an int32 label
+// code or an fp32 raw value: a job uploads a column's whole grid once and pass g points at element
+// g). The value goes through the same code < cat_size test / the same (x - mean) / std as a value
+// read from the table, so the unknown index and the dropped last category give the all-zero block.
+// const_src is a kernel argument, so the branch is uniform: the column's wave reads one scalar
+// instead of 64 rows, every other column is read as before. const_src = -1 (and perm_src = -1):
+// the plain launch. At most one of perm_src / const_src is set (the launcher refuses both).
 #include "common.h"
 #include "kernels.h"
 
@@ -69,7 +78,7 @@ __global__ __launch_bounds__(kAsmThreads) void assemble_features_kernel(
     const int* __restrict__ codes, const float* __restrict__ cont, const int* __restrict__ cat_off,
     const int* __restrict__ cat_size, const float* __restrict__ mean, const float* __restrict__ stdv, long N, int C,
     int Q, int F, int ld, OutT* __restrict__ out, long ld_src, int perm_src, const int* __restrict__ perm,
-    const void* __restrict__ perm_base, long perm_n) {
+    const void* __restrict__ perm_base, long perm_n, int const_src, const void* __restrict__ const_val) {
   extern __shared__ unsigned asm_tile[];  // [kAsmRows][Dp] dwords
   constexpr int EPD = 4 / (int)sizeof(OutT);  // elements per dword
   const int D = ld / EPD;                     // dwords per output row (bf16: ld % 8 == 0)
@@ -88,19 +97,24 @@ __global__ __launch_bounds__(kAsmThreads) void assemble_features_kernel(
       OutT* const trow = telem + (long)lane * Dp * EPD;
       for (int s = wave; s < C + Q; s += kAsmThreads / 64) {
         const bool permuted = s == perm_src;  // wave-uniform
+        const bool constant = s == const_src;  // uniform: the same value for every row
         long pr = 0;
         if (permuted) {
           pr = perm[row0 + lane];
           pr = pr < 0 ? 0 : (pr >= perm_n ? perm_n - 1 : pr);
         }
         if (s < C) {
-          const int code = permuted ? static_cast<const int*>(perm_base)[pr] : codes[(long)s * ld_src + row0 + lane];
+          const int code = constant   ? *static_cast<const int*>(const_val)
+                           : permuted ? static_cast<const int*>(perm_base)[pr]
+                                      : codes[(long)s * ld_src + row0 + lane];
           const int col = cat_off[s] + code;
           // col < Fc also when the block spec itself were wrong: never a write outside the row
           if ((unsigned)code < (unsigned)cat_size[s] && (unsigned)col < (unsigned)Fc) trow[col] = AsmOut<OutT>::cvt(1.0f);
         } else {
           const int q = s - C;
-          const float x = permuted ? static_cast<const float*>(perm_base)[pr] : cont[(long)q * ld_src + row0 + lane];
+          const float x = constant   ? *static_cast<const float*>(const_val)
+                          : permuted ? static_cast<const float*>(perm_base)[pr]
+                                     : cont[(long)q * ld_src + row0 + lane];
           trow[Fc + q] = AsmOut<OutT>::cvt((x - mean[q]) / stdv[q]);
         }
       }
@@ -148,8 +162,11 @@ template <typename OutT>
 static bool launch_assemble(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                             const float* mean, const float* stdv, long N, int C, int Q, int F, int ld, OutT* out,
                             hipStream_t s, const AssemblePerm& pm) {
-  // a permuted source needs its index vector and a non-empty column to clamp into
-  if (pm.src >= 0 && (pm.src >= C + Q || pm.perm == nullptr || pm.base == nullptr || pm.n < 1)) return false;
+  // a permuted source needs its index vector and a non-empty column to clamp into; a broadcast
+  // source its one value, and no index vector (the two modes exclude each other)
+  if (pm.src >= 0 && !pm.broadcast && (pm.src >= C + Q || pm.perm == nullptr || pm.base == nullptr || pm.n < 1))
+    return false;
+  if (pm.broadcast && (pm.src < 0 || pm.src >= C + Q || pm.value == nullptr || pm.perm != nullptr)) return false;
   if (pm.ld_src != 0 && pm.ld_src < N) return false;
   const size_t lds = assemble_features_lds_bytes(ld, sizeof(OutT) == 2);
   if (lds > kAssembleMaxLds) return false;
@@ -162,7 +179,8 @@ static bool launch_assemble(const int* codes, const float* cont, const int* cat_
   // capped grid: 8 workgroups per CU of a 256-CU device keep ~0.5 MB of column reads in flight
   const long grid = ntiles < 2048 ? ntiles : 2048;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kAsmThreads), lds, s, codes, cont, cat_off, cat_size, mean, stdv,
-                     N, C, Q, F, ld, out, pm.ld_src ? pm.ld_src : N, pm.src >= 0 ? pm.src : -1, pm.perm, pm.base, pm.n);
+                     N, C, Q, F, ld, out, pm.ld_src ? pm.ld_src : N, pm.src >= 0 && !pm.broadcast ? pm.src : -1, pm.perm,
+                     pm.base, pm.n, pm.broadcast ? pm.src : -1, pm.value);
   return true;
 }
 

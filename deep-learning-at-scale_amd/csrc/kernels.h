@@ -309,12 +309,17 @@ size_t assemble_features_lds_bytes(int ld, bool bf16_out);
 // piece of a larger table), and ONE source column src in [0, C + Q) (categorical first) read
 // through a row permutation: output row r takes base[clamp(perm[r], 0, n - 1)], base / n the
 // whole source column (int32 codes or fp32 values). src = -1: none.
+// broadcast = true: source column src is a CONSTANT instead: every output row takes *value (one
+// int32 code or one fp32 raw value on the device), which goes through the same block test /
+// standardisation as a table value; perm stays nullptr.
 struct AssemblePerm {
   long ld_src = 0;
   int src = -1;
   const int* perm = nullptr;
   const void* base = nullptr;
   long n = 0;
+  bool broadcast = false;
+  const void* value = nullptr;
 };
 bool launch_assemble_features_bf16(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                                    const float* mean, const float* stdv, long N, int C, int Q, int F, int ld,
@@ -331,5 +336,19 @@ constexpr int kErrSumsMaxBlocks = 256;
 constexpr int kErrSumsScratch = 2 * kErrSumsMaxBlocks + 1;
 void launch_err_sums(const float* pred, const float* y, long M, double y_scale, double y_shift, double* out2,
                      double* scratch, hipStream_t s);
+
+// ---- grouped prediction sums (score.hip) ----
+// v = (double)pred * y_scale + y_shift; out [G][3] = {n_g, sum v, sum v * v} per group, fp64, from a
+// host-built plan: order int32 [M] (a stable argsort of the group ids), every group's run in
+// `order` cut into pieces of at most kGroupPiece positions (piece_first / piece_len int32
+// [pieces]), group_pieces int32 [G + 1] (group g owns pieces [group_pieces[g], group_pieces[g + 1])).
+// partial: 3 * pieces doubles of scratch, no state between launches. Two stream-ordered launches;
+// bitwise repeatable for a given plan (the order of additions depends on kGroupPiece: do not
+// change it without saying so). false = refused, nothing launched.
+constexpr int kGroupPiece = 1024;
+constexpr int kGroupSumsMaxGroups = 16384;
+bool launch_group_sums(const float* pred, const int* order, const int* piece_first, const int* piece_len,
+                       const int* group_pieces, long M, int pieces, int G, double y_scale, double y_shift,
+                       double* out, double* partial, hipStream_t s);
 
 }  // namespace wf

@@ -1,4 +1,5 @@
-// wellflow — scoring-error reduction on the device (gfx950).
+// wellflow — scoring reductions on the device (gfx950): the error sums of a pass (err_sums, below)
+// and the grouped prediction sums of a pass (group_sums, second half of this file).
 //
 // A permutation-importance run (wellflow/importance.py) scores the table 1 + columns x repeats
 // times; every pass ends in this kernel instead of a D2H copy of the predictions and a host
@@ -110,6 +111,143 @@ void launch_err_sums(const float* pred, const float* y, long M, double y_scale, 
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(err_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pred, y, M, y_scale, y_shift, out2,
                      scratch);
+}
+
+// ---- grouped prediction sums (response curves, wellflow/response.py) ----
+//
+// A response-curve run scores the table 1 + sum(grid sizes) times and wants, per pass, the mean
+// prediction of every group (a well, say). For v = (double)pred * y_scale + y_shift (the
+// pipeline's inverse_target in fp64: a correctly rounded mul and add, never fused, so v equals
+// numpy's float64 value bit for bit)
+//   out[g] = { n_g, sum v, sum v * v }        for every group g in [0, G).
+//
+// The grouping is the same for every pass, so the host builds a PLAN once (ops/native.py
+// GroupPlan): `order`, a stable argsort of the group ids (pred is read through it: the identity,
+// a coalesced read, when the rows are already grouped; a 4-B gather otherwise), and every group's
+// run in `order` cut into pieces of at most kGroupPiece positions. Two plain launches on the stream:
+//   A. one wave per piece (grid-stride, capped grid): lane l adds positions l, l + 64, .. of the
+//      piece in that order, a fixed xor tree joins the lanes, lane 0 stores partial[piece];
+//   B. one wave per group (grid-stride): lane l adds the group's pieces l, l + 64, .. in index
+//      order, the same tree, lane 0 stores out[g] (zeros for a group without pieces).
+// B starts after A has finished (stream order), so there is no fence, no ticket and no scratch
+// state to leave ready; no float atomics, nothing waits or spins. The order of additions is a
+// function of the plan alone (of the group layout and kGroupPiece), so the sums are bitwise
+// repeatable. A NaN prediction reaches the partials of its own group only.
+// Every index read from the plan is clamped into its array, so a wrong plan gives wrong sums,
+// never an access outside pred / order / partial.
+namespace {
+
+constexpr int kGroupWaves = 4;  // waves (pieces / groups in flight) per workgroup
+
+__device__ __forceinline__ double group_value(float p, double y_scale, double y_shift) {
+#pragma clang fp contract(off)
+  const double a = (double)p * y_scale;
+  return a + y_shift;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64 * kGroupWaves) void group_partial_kernel(
+    const float* __restrict__ pred, const int* __restrict__ order, const int* __restrict__ piece_first,
+    const int* __restrict__ piece_len, long M, int pieces, double y_scale, double y_shift,
+    double* __restrict__ partial) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (long pc = (long)blockIdx.x * kGroupWaves + wave; pc < pieces; pc += (long)gridDim.x * kGroupWaves) {
+    long first = piece_first[pc];
+    int len = piece_len[pc];
+    first = first < 0 ? 0 : (first > M ? M : first);
+    len = len < 0 ? 0 : (len > kGroupPiece ? kGroupPiece : len);
+    if (first + len > M) len = (int)(M - first);
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = lane; i < len; i += 4 * 64) {  // four strided positions per trip: the loads overlap
+      float p[4];
+      bool ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = i + 64 * u;
+        ok[u] = j < len;
+        long r = ok[u] ? order[first + j] : 0;
+        r = r < 0 ? 0 : (r >= M ? M - 1 : r);
+        p[u] = pred[r];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (ok[u]) {
+          const double v = group_value(p[u], y_scale, y_shift);
+          s1 += v;
+          s2 += v * v;
+        }
+      }
+    }
+    s1 = wave_sum_f64(s1);
+    s2 = wave_sum_f64(s2);
+    if (lane == 0) {
+      partial[3 * pc] = (double)len;
+      partial[3 * pc + 1] = s1;
+      partial[3 * pc + 2] = s2;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64 * kGroupWaves) void group_finish_kernel(const double* __restrict__ partial,
+                                                                        const int* __restrict__ group_pieces,
+                                                                        int pieces, int G, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (long g = (long)blockIdx.x * kGroupWaves + wave; g < G; g += (long)gridDim.x * kGroupWaves) {
+    int p0 = group_pieces[g], p1 = group_pieces[g + 1];
+    p0 = p0 < 0 ? 0 : (p0 > pieces ? pieces : p0);
+    p1 = p1 < p0 ? p0 : (p1 > pieces ? pieces : p1);
+    double n = 0.0, s1 = 0.0, s2 = 0.0;
+    // four strided pieces per trip: their loads overlap (one group of a large table has thousands
+    // of pieces and ONE wave to walk them); added in index order all the same
+    for (int pc = p0 + lane; pc < p1; pc += 4 * 64) {
+      double a[4][3];
+      bool ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        ok[u] = pc + 64 * u < p1;
+        const long q = 3 * (long)(ok[u] ? pc + 64 * u : p0);
+        a[u][0] = partial[q];
+        a[u][1] = partial[q + 1];
+        a[u][2] = partial[q + 2];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (ok[u]) {
+          n += a[u][0];
+          s1 += a[u][1];
+          s2 += a[u][2];
+        }
+      }
+    }
+    n = wave_sum_f64(n);
+    s1 = wave_sum_f64(s1);
+    s2 = wave_sum_f64(s2);
+    if (lane == 0) {
+      const bool empty = p1 == p0;
+      out[3 * g] = empty ? 0.0 : n;
+      out[3 * g + 1] = empty ? 0.0 : s1;
+      out[3 * g + 2] = empty ? 0.0 : s2;
+    }
+  }
+}
+
+bool launch_group_sums(const float* pred, const int* order, const int* piece_first, const int* piece_len,
+                       const int* group_pieces, long M, int pieces, int G, double y_scale, double y_shift,
+                       double* out, double* partial, hipStream_t s) {
+  if (M < 1 || M > 2147483647L || pieces < 1 || G < 1 || G > kGroupSumsMaxGroups) return false;
+  // capped grids, grid-stride over the rest: 8 workgroups per CU of a 256-CU device
+  long ba = ((long)pieces + kGroupWaves - 1) / kGroupWaves;
+  if (ba > 2048) ba = 2048;
+  long bb = ((long)G + kGroupWaves - 1) / kGroupWaves;
+  if (bb > 2048) bb = 2048;
+  hipLaunchKernelGGL(group_partial_kernel, dim3((unsigned)ba), dim3(64 * kGroupWaves), 0, s, pred, order, piece_first,
+                     piece_len, M, pieces, y_scale, y_shift, partial);
+  hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)bb), dim3(64 * kGroupWaves), 0, s, partial, group_pieces,
+                     pieces, G, out);
+  return true;
 }
 
 }  // namespace wf

@@ -96,13 +96,19 @@ class ResidentColumns:
 
         return (self.F + 7) // 8 * 8 if out_dtype == torch.bfloat16 else self.F
 
-    def assemble(self, out_dtype, rows=None, perm=None, perm_col: int = -1, out=None):
+    def assemble(self, out_dtype, rows=None, perm=None, perm_col: int = -1, out=None, const_col: int = -1,
+                 const_value=None):
         """Feature rows ``rows = (a, b)`` (default: all) of the resident table, as
         :func:`assemble_features` builds them. With ``perm`` (int32 device vector of ``b - a``
         indices into ALL N rows) source column ``perm_col`` — in the kernel's source order, the C
         categorical columns first, then the Q continuous ones — is read through it: output row r
         takes that column's value of row ``perm[r]`` (the kernel clamps the index into the
-        column). Everything is refused here, on the host, before a launch; nothing is uploaded."""
+        column). With ``const_value`` (a contiguous one-element tensor on the table's device: an
+        int32 label code for a categorical source, a float32 raw value for a continuous one)
+        source column ``const_col`` is that constant in every output row; it goes through the
+        kernel's own block test / standardisation, so the unknown index ``len(labels)`` gives the
+        all-zero block. One column is permuted or constant, not both.
+        Everything is refused here, on the host, before a launch; nothing is uploaded."""
         import torch
 
         a, b = (0, self.N) if rows is None else (int(rows[0]), int(rows[1]))
@@ -120,13 +126,32 @@ class ResidentColumns:
                 raise TypeError(f"assemble_features: perm must be int32, got {perm.dtype}")
             if perm.dim() != 1 or perm.numel() != b - a or not perm.is_contiguous():
                 raise ValueError(f"assemble_features: perm holds {tuple(perm.shape)} indices for {b - a} rows")
+        const_col = int(const_col)
+        if (const_value is None) != (const_col < 0):
+            raise ValueError("assemble_features: const_col and const_value go together")
+        if const_value is not None:
+            if perm is not None:
+                raise ValueError("assemble_features: one source column is permuted or constant, not both "
+                                 "(perm and const_col)")
+            if not 0 <= const_col < self.C + self.Q:
+                raise ValueError(f"assemble_features: const_col {const_col} outside [0, {self.C + self.Q})")
+            if not isinstance(const_value, torch.Tensor) or const_value.device != self.device:
+                raise ValueError(f"assemble_features: const_value must be a tensor on {self.device}")
+            want = torch.int32 if const_col < self.C else torch.float32
+            if const_value.dtype != want:
+                raise TypeError(f"assemble_features: const_value must be {want} for a "
+                                f"{'categorical' if const_col < self.C else 'continuous'} column, got {const_value.dtype}")
+            if const_value.numel() != 1 or not const_value.is_contiguous():
+                raise ValueError(f"assemble_features: const_value must be one contiguous element, got "
+                                 f"{tuple(const_value.shape)}")
         ld = self.out_width(out_dtype)
         if out is None:
             out = torch.empty((b - a, ld), dtype=out_dtype, device=self.device)
         elif out.shape != (b - a, ld) or out.dtype != out_dtype or out.device != self.device:
             raise ValueError(f"assemble_features: out must be {out_dtype} [{b - a}][{ld}] on {self.device}")
         lib().assemble_features(self.codes, self.cont, self.off, self.size, self.mean, self.std, a, b - a, self.F, out,
-                                perm_col if perm is not None else -1, perm)
+                                perm_col if perm is not None else -1, perm, const_col if const_value is not None else -1,
+                                const_value)
         return out
 
 
@@ -154,6 +179,80 @@ def err_sums_scratch(device):
     import torch
 
     return torch.zeros(ERR_SUMS_SCRATCH, dtype=torch.float64, device=device)
+
+
+GROUP_PIECE = 1024  # csrc/kernels.h kGroupPiece: positions per piece; the order of additions depends on it
+GROUP_SUMS_MAX_GROUPS = 16384  # csrc/kernels.h kGroupSumsMaxGroups: out is passes x G x 24 bytes
+
+
+class GroupPlan:
+    """How :func:`group_sums` reduces M predictions into G groups: built ONCE per table on the
+    host (the grouping is the same for every pass of a run) and uploaded.
+
+    ``ids``: one group id in [0, G) per prediction (any integer array). The plan holds
+    ``order`` int32 [M], a stable argsort of the ids (predictions are read through it: the
+    identity when they are already grouped); every group's run in ``order`` cut into pieces of at
+    most ``GROUP_PIECE`` positions — ``pieces`` int32 [2][P]: first position and length, and
+    ``piece_group`` (host, int32 [P]) — ``group_pieces`` int32 [G + 1]: group g owns the pieces
+    [group_pieces[g], group_pieces[g + 1]) (none: an empty group); and the scratch buffer
+    (fp64 [3 P], no state between launches). ``counts`` (host, int64 [G]): rows per group."""
+
+    def __init__(self, ids, G: int, device):
+        import numpy as np
+        import torch
+
+        self.device = dev = torch.device(device)
+        self.G = G = int(G)
+        if not 1 <= G <= GROUP_SUMS_MAX_GROUPS:
+            raise ValueError(f"group_sums: {G} groups (need 1 .. {GROUP_SUMS_MAX_GROUPS})")
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise TypeError(f"group_sums: the group ids must be a vector of integers, got {ids.dtype} {ids.shape}")
+        self.M = M = len(ids)
+        if not 1 <= M < 2 ** 31:
+            raise ValueError(f"group_sums: {M} predictions (need 1 .. 2^31 - 1)")
+        ids = ids.astype(np.int64)
+        if ids.min() < 0 or ids.max() >= G:
+            bad = ids[(ids < 0) | (ids >= G)][0]
+            raise ValueError(f"group_sums: group id {int(bad)} outside [0, {G})")
+        order = np.argsort(ids, kind="stable")
+        self.counts = counts = np.bincount(ids, minlength=G).astype(np.int64)
+        npieces = (counts + GROUP_PIECE - 1) // GROUP_PIECE
+        gp = np.concatenate([[0], np.cumsum(npieces)]).astype(np.int64)
+        group = np.repeat(np.arange(G, dtype=np.int64), npieces)
+        k = np.arange(int(gp[-1]), dtype=np.int64) - gp[group]  # the piece's index inside its group
+        first = (np.cumsum(counts) - counts)[group] + k * GROUP_PIECE
+        length = np.minimum(GROUP_PIECE, counts[group] - k * GROUP_PIECE)
+        self.piece_group = group.astype(np.int32)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+        self.order, self.pieces, self.group_pieces = i32(order), i32(np.stack([first, length])), i32(gp)
+        self.scratch = torch.zeros(3 * int(gp[-1]), dtype=torch.float64, device=dev)
+
+
+def group_sums(pred, plan: GroupPlan, y_scale: float, y_shift: float, out, slot: int):
+    """``out[slot][g] = {n_g, sum v, sum v * v}``, ``v = pred * y_scale + y_shift`` in fp64, per
+    group of ``plan`` (csrc/score.hip): ``pred`` fp32 device vector [plan.M], ``out`` fp64
+    [S][plan.G][3]. An empty group gives zeros; a NaN prediction makes only its own group's sums
+    NaN. No float atomics: bitwise repeatable for a given plan. Stream-ordered; nothing comes back
+    to the host."""
+    import torch
+
+    if not isinstance(plan, GroupPlan):
+        raise TypeError("group_sums: plan must be a GroupPlan")
+    if not isinstance(pred, torch.Tensor) or pred.dtype != torch.float32:
+        raise TypeError(f"group_sums: pred must be a float32 tensor, got {getattr(pred, 'dtype', type(pred))}")
+    if pred.device != plan.device:
+        raise ValueError(f"group_sums: pred is on {pred.device}, the plan on {plan.device}")
+    if pred.dim() != 1 or pred.numel() != plan.M or not pred.is_contiguous():
+        raise ValueError(f"group_sums: pred holds {tuple(pred.shape)} predictions, the plan groups {plan.M}")
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float64:
+        raise TypeError(f"group_sums: out must be a float64 tensor, got {getattr(out, 'dtype', type(out))}")
+    if out.device != plan.device or out.dim() != 3 or tuple(out.shape[1:]) != (plan.G, 3) or not out.is_contiguous():
+        raise ValueError(f"group_sums: out must be float64 [S][{plan.G}][3] on {plan.device}, got {tuple(out.shape)}")
+    if not 0 <= int(slot) < out.shape[0]:
+        raise ValueError(f"group_sums: slot {slot} outside [0, {out.shape[0]})")
+    lib().group_sums(pred, plan.order, plan.pieces, plan.group_pieces, float(y_scale), float(y_shift), out, int(slot),
+                     plan.scratch)
 
 
 def gemm(A, B, M, N, K, *, a_mn=False, lda=None, b_mn=False, ldb=None, outF=None, outH=None,

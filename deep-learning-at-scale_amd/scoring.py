@@ -13,9 +13,13 @@ routes:
 * the fp32 oracle (CPU, or fp32 on a GPU): host rows through the PyTorch engine.
 
 ``score(k, perm)`` returns the network outputs as fp32 ``[M]``: a device tensor (the pass's own
-buffer) on the native routes, a numpy array from the oracle.
+buffer) on the native routes, a numpy array from the oracle. Source column ``k`` is read through
+the permutation ``perm`` (importance.py) or, with ``const``, set to one constant in every row
+(response.py); without either the table is scored as it is.
 """
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 import torch
@@ -28,6 +32,22 @@ HBM_TABLE_FRACTION = 8  # an assembled MLP table above 1/8 of HBM is assembled a
 def permuted(table: dict, col: str, perm) -> dict:
     t = dict(table)
     t[col] = np.asarray(table[col])[np.asarray(perm, dtype=np.int64)]
+    return t
+
+
+# One source column set to a constant. ``host``: the label (str) of a categorical column or the
+# np.float32 raw value of a continuous one, what the host routes write into the table; ``dev``: the
+# same value as a one-element device tensor (the int32 label code / the float32 value: an element
+# of a grid that was uploaded once), what the device assembly reads.
+Constant = collections.namedtuple("Constant", ["host", "dev"], defaults=[None])
+
+
+def constant(table: dict, col: str, value) -> dict:
+    """The table with column ``col`` set to ``value`` in every row: a label (str) gives an object
+    column, anything else a float32 column (the pipeline casts continuous columns to float32)."""
+    n = len(next(iter(table.values())))
+    t = dict(table)
+    t[col] = np.full(n, value, object) if isinstance(value, str) else np.full(n, value, np.float32)
     return t
 
 
@@ -57,22 +77,29 @@ class _Pass:
         pipe = self.pipe
         return ResidentColumns(codes, cont, *pipe.block_spec(), *pipe.scale(), self.pred.n_features, self.pred.device)
 
-    def _features(self, k: int, perm) -> np.ndarray:
-        """The host pipeline's rows, source column ``k`` read through ``perm``."""
+    def _features(self, k: int, perm, const=None) -> np.ndarray:
+        """The host pipeline's rows, source column ``k`` read through ``perm`` or set to ``const``."""
+        if k >= 0 and const is not None:
+            return self.pipe.features(constant(self.table, self.names[k], const.host))
         tab = self.table if k < 0 else permuted(self.table, self.names[k], torch.as_tensor(perm).cpu().numpy())
         return self.pipe.features(tab)
 
     def _input_format(self, X: torch.Tensor) -> torch.Tensor:
         return X
 
-    def assemble(self, a: int, b: int, k: int = -1, perm=None, host=None) -> torch.Tensor:
+    def assemble(self, a: int, b: int, k: int = -1, perm=None, host=None, const=None) -> torch.Tensor:
         """Rows [a, b) of the table as engine input, in the pass's piece buffer. Device assembly:
         source column ``k`` (or -1) is read through ``perm`` (int32 device vector over ALL rows;
-        resident columns only). ``host``: the host-built rows of the whole table instead (host
-        assembly with the native engine)."""
+        resident columns only) or set to ``const.dev`` (a :class:`Constant`; resident columns
+        only). ``host``: the host-built rows of the whole table instead (host assembly with the
+        native engine)."""
         X = self.X[: b - a]
         if host is not None:
             X.copy_(self._input_format(torch.from_numpy(host[a:b])))
+        elif k >= 0 and const is not None:
+            if self.res is None:
+                raise ValueError("a constant pass reads resident columns (resident=True)")
+            self.res.assemble(self.dtype, rows=(a, b), const_col=k, const_value=const.dev, out=X)
         elif self.res is not None:
             self.res.assemble(self.dtype, rows=(a, b), perm=None if k < 0 else perm[a:b], perm_col=k, out=X)
         else:  # this piece's raw columns alone go up
@@ -81,13 +108,14 @@ class _Pass:
             self._resident(self.codes[:, a:b], self.cont[:, a:b]).assemble(self.dtype, out=X)
         return X
 
-    def score(self, k: int = -1, perm=None):
-        """Network outputs fp32 [M], source column ``k`` (or -1: none) read through ``perm``."""
+    def score(self, k: int = -1, perm=None, const=None):
+        """Network outputs fp32 [M], source column ``k`` (or -1: none) read through ``perm`` or,
+        with ``const`` (a :class:`Constant`), set to that value in every row."""
         if not self.native:
-            return self._score_host(self._features(k, perm))
-        host = None if self.on_device else self._features(k, perm)
+            return self._score_host(self._features(k, perm, const))
+        host = None if self.on_device else self._features(k, perm, const)
         for a, b in self.pieces:
-            self.forward(self.assemble(a, b, k, perm, host), a)
+            self.forward(self.assemble(a, b, k, perm, host, const), a)
         return self.p
 
 

@@ -8,6 +8,10 @@ scores a CSV with the ``.mdl`` a training job saved (wellflow/predict.py).
 
 ``python -m wellflow.submit importance <model> columnNames columnTypes targetColumn storagePath dataPath``
 ranks the input columns of that ``.mdl`` by permutation importance (wellflow/importance.py).
+
+``python -m wellflow.submit response <model> columnNames columnTypes targetColumn storagePath dataPath --columns a[,b..]``
+sweeps one input column at a time over a grid and writes the mean prediction per value, overall and
+per ``--by`` group: the model's response curves (wellflow/response.py).
 """
 import sys
 
@@ -27,6 +31,10 @@ def main(argv=None) -> int:
         from .importance import main as importance_main
 
         return importance_main(argv[1:])
+    if argv[0] == "response":  # response curves of a saved .mdl: one input column set to a grid of values
+        from .response import main as response_main
+
+        return response_main(argv[1:])
     run_job(argv[0], argv[1:])
     return 0
 
