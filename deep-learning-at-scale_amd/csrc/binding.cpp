@@ -965,13 +965,17 @@ void transpose_cast_bf16(const at::Tensor& src, int64_t lds, int64_t rows, int64
 // [0, C + Q) (else -1 and const_value None; not together with perm) that source column is the
 // CONSTANT const_value[0] instead, a one-element device tensor: an int32 label code for a
 // categorical column, an fp32 raw value for a continuous one: the response-curve pass.
+// With set_mask (int32 [ceil((C + Q) / 32)] on the table's device, the bit pattern of the mask's
+// 32-bit words: bit s & 31 of word s >> 5 is source column s; perm given, perm_col and const_col
+// -1) EVERY source column of the set is read through `perm`: the Shapley-attribution pass.
 constexpr int64_t kAssembleMaxF = 512;
 
 void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
                        c10::optional<at::Tensor> cat_off, c10::optional<at::Tensor> cat_size,
                        c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t row0, int64_t N,
                        int64_t F, const at::Tensor& out, int64_t perm_col, c10::optional<at::Tensor> perm,
-                       int64_t const_col, c10::optional<at::Tensor> const_value) {
+                       int64_t const_col, c10::optional<at::Tensor> const_value,
+                       c10::optional<at::Tensor> set_mask) {
   const bool has_c = codes.has_value() && codes->defined() && codes->numel() > 0;
   const bool has_q = cont.has_value() && cont->defined() && cont->numel() > 0;
   int64_t Ntot = -1;
@@ -1013,8 +1017,31 @@ void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor
   wf::AssemblePerm pm;
   pm.ld_src = Ntot;
   const bool has_p = perm.has_value() && perm->defined();
-  TORCH_CHECK(has_p == (perm_col >= 0), "assemble_features: perm and perm_col go together");
-  if (has_p) {
+  const bool has_s = set_mask.has_value() && set_mask->defined();
+  if (has_s) {
+    TORCH_CHECK(perm_col < 0, "assemble_features: a set of permuted columns or ONE perm_col, not both");
+    TORCH_CHECK(const_col < 0 && !(const_value.has_value() && const_value->defined()),
+                "assemble_features: a set of permuted columns is not combined with a constant column");
+    TORCH_CHECK(has_p, "assemble_features: a set of permuted columns needs perm");
+    TORCH_CHECK(set_mask->is_cuda() && set_mask->device() == out.device() && set_mask->scalar_type() == at::kInt &&
+                    set_mask->is_contiguous() && set_mask->dim() == 1,
+                "assemble_features: set_mask must be a contiguous int32 vector on the table's device");
+    TORCH_CHECK(set_mask->numel() == (C + Q + 31) / 32, "assemble_features: set_mask holds ", set_mask->numel(),
+                " words for ", C + Q, " source columns (need ", (C + Q + 31) / 32, ")");
+    TORCH_CHECK(perm->is_cuda() && perm->device() == out.device() && perm->scalar_type() == at::kInt &&
+                    perm->is_contiguous() && perm->dim() == 1,
+                "assemble_features: perm must be a contiguous int32 GPU vector");
+    TORCH_CHECK(perm->numel() == N, "assemble_features: perm holds ", perm->numel(), " indices for ", N, " rows");
+    TORCH_CHECK(Ntot <= INT32_MAX, "assemble_features: int32 perm cannot index ", Ntot, " rows");
+    pm.perm = perm->data_ptr<int>();
+    pm.n = Ntot;
+    pm.set_mask = reinterpret_cast<const unsigned*>(set_mask->data_ptr<int>());
+    pm.codes0 = cp;
+    pm.cont0 = xp;
+  } else {
+    TORCH_CHECK(has_p == (perm_col >= 0), "assemble_features: perm and perm_col go together");
+  }
+  if (has_p && !has_s) {
     TORCH_CHECK(perm_col < C + Q, "assemble_features: perm_col ", perm_col, " outside 0 .. ", C + Q - 1);
     TORCH_CHECK(perm->is_cuda() && perm->scalar_type() == at::kInt && perm->is_contiguous() && perm->dim() == 1,
                 "assemble_features: perm must be a contiguous int32 GPU vector");
@@ -1071,6 +1098,36 @@ void err_sums(const at::Tensor& pred, const at::Tensor& y, double y_scale, doubl
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(pred.device());
   wf::launch_err_sums(pred.data_ptr<float>(), y.data_ptr<float>(), pred.numel(), y_scale, y_shift,
                       out.data_ptr<double>() + 2 * slot, scratch.data_ptr<double>(), cur_stream());
+}
+
+// Per-row attribution accumulation (score.hip): one step of a sampling Shapley run. p_cur / p_prev
+// fp32 [M] (not overlapping), acc / sq contiguous fp64 [K + 1][M]; row `row` of both is updated
+// (start: v = p_cur * y_scale + y_shift; else d = (p_cur - p_prev) * y_scale; acc += ., sq += .^2,
+// uncontracted fp64) and p_prev = p_cur. Stream-ordered; nothing is read back here.
+void attr_step(const at::Tensor& p_cur, const at::Tensor& p_prev, double y_scale, double y_shift, const at::Tensor& acc,
+               const at::Tensor& sq, int64_t row, bool start) {
+  for (const at::Tensor* t : {&p_cur, &p_prev}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 1,
+                "attr_step: p_cur / p_prev must be contiguous fp32 GPU vectors");
+  }
+  const int64_t M = p_cur.numel();
+  TORCH_CHECK(M >= 1 && p_prev.numel() == M, "attr_step: p_cur holds ", M, " elements, p_prev ", p_prev.numel(),
+              " (need the same, >= 1)");
+  const char* a0 = static_cast<const char*>(p_cur.data_ptr());
+  const char* b0 = static_cast<const char*>(p_prev.data_ptr());
+  TORCH_CHECK(a0 + 4 * M <= b0 || b0 + 4 * M <= a0, "attr_step: p_cur and p_prev overlap");
+  for (const at::Tensor* t : {&acc, &sq}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kDouble && t->is_contiguous() &&
+                    t->dim() == 2 && t->size(1) == M,
+                "attr_step: acc / sq must be contiguous fp64 [K + 1][", M, "] GPU tensors");
+    TORCH_CHECK(t->device() == p_cur.device(), "attr_step: tensors on different devices");
+  }
+  TORCH_CHECK(acc.size(0) == sq.size(0) && acc.data_ptr() != sq.data_ptr(), "attr_step: acc and sq must be two tables of one shape");
+  TORCH_CHECK(p_prev.device() == p_cur.device(), "attr_step: tensors on different devices");
+  TORCH_CHECK(row >= 0 && row < acc.size(0), "attr_step: row ", row, " outside 0 .. ", acc.size(0) - 1);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p_cur.device());
+  wf::launch_attr_step(p_cur.data_ptr<float>(), p_prev.data_ptr<float>(), M, y_scale, y_shift,
+                       acc.data_ptr<double>() + row * M, sq.data_ptr<double>() + row * M, start, cur_stream());
 }
 
 // Grouped prediction sums (score.hip): out[slot][g] = {n_g, sum v, sum v^2}, v = pred * y_scale +
@@ -1429,12 +1486,14 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(gather_rows);
   WF_DEF(transpose_cast_bf16);
   WF_DEF(im2col1d);
-  // const_col / const_value are optional (and keywords): the twelve-argument call is the launch it was
+  // const_col / const_value / set_mask are optional (and keywords): the twelve-argument call is the launch it was
   m.def("assemble_features", &Checked<&assemble_features>::call, py::arg("codes"), py::arg("cont"), py::arg("cat_off"),
         py::arg("cat_size"), py::arg("mean"), py::arg("std"), py::arg("row0"), py::arg("N"), py::arg("F"), py::arg("out"),
-        py::arg("perm_col"), py::arg("perm"), py::arg("const_col") = -1, py::arg("const_value") = py::none());
+        py::arg("perm_col"), py::arg("perm"), py::arg("const_col") = -1, py::arg("const_value") = py::none(),
+        py::arg("set_mask") = py::none());
   WF_DEF(err_sums);
   WF_DEF(group_sums);
+  WF_DEF(attr_step);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
   m.def("cnn_fused_ok", &cnn_fused_ok);

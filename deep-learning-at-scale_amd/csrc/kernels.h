@@ -320,6 +320,14 @@ struct AssemblePerm {
   long n = 0;
   bool broadcast = false;
   const void* value = nullptr;
+  // A SET of source columns read through `perm` instead (src = -1, no broadcast, base nullptr):
+  // set_mask is a device bitmask over the C + Q source columns (bit s & 31 of word s >> 5), codes0 /
+  // cont0 row 0 of the whole table (columns ld_src apart, which must be given) and n the column
+  // length: output row r takes column s of row clamp(perm[r], 0, n - 1) for every s in the set.
+  // A separate kernel instantiation: the launches above run the code they ran without it.
+  const unsigned* set_mask = nullptr;
+  const int* codes0 = nullptr;
+  const float* cont0 = nullptr;
 };
 bool launch_assemble_features_bf16(const int* codes, const float* cont, const int* cat_off, const int* cat_size,
                                    const float* mean, const float* stdv, long N, int C, int Q, int F, int ld,
@@ -336,6 +344,16 @@ constexpr int kErrSumsMaxBlocks = 256;
 constexpr int kErrSumsScratch = 2 * kErrSumsMaxBlocks + 1;
 void launch_err_sums(const float* pred, const float* y, long M, double y_scale, double y_shift, double* out2,
                      double* scratch, hipStream_t s);
+
+// ---- per-row attribution accumulation (score.hip) ----
+// One step of a sampling Shapley run over M >= 1 predictions, fp64, never contracted:
+//   start:  v = (double)p_cur[i] * y_scale + y_shift;              acc[i] += v; sq[i] += v * v
+//   else:   d = ((double)p_cur[i] - (double)p_prev[i]) * y_scale;  acc[i] += d; sq[i] += d * d
+// then p_prev[i] = p_cur[i]. acc / sq point at the row of the job's [K + 1][M] tables that the step
+// belongs to. One thread per cell, plain loads and stores: bitwise equal to a numpy float64 replay.
+// p_cur and p_prev must not overlap.
+void launch_attr_step(const float* p_cur, float* p_prev, long M, double y_scale, double y_shift, double* acc,
+                      double* sq, bool start, hipStream_t s);
 
 // ---- grouped prediction sums (score.hip) ----
 // v = (double)pred * y_scale + y_shift; out [G][3] = {n_g, sum v, sum v * v} per group, fp64, from a

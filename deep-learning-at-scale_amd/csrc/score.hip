@@ -1,5 +1,6 @@
-// wellflow — scoring reductions on the device (gfx950): the error sums of a pass (err_sums, below)
-// and the grouped prediction sums of a pass (group_sums, second half of this file).
+// wellflow — scoring reductions on the device (gfx950): the error sums of a pass (err_sums, below),
+// the per-row attribution accumulation over two passes (attr_step) and the grouped prediction sums
+// of a pass (group_sums, last part of this file).
 //
 // A permutation-importance run (wellflow/importance.py) scores the table 1 + columns x repeats
 // times; every pass ends in this kernel instead of a D2H copy of the predictions and a host
@@ -111,6 +112,61 @@ void launch_err_sums(const float* pred, const float* y, long M, double y_scale, 
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(err_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pred, y, M, y_scale, y_shift, out2,
                      scratch);
+}
+
+// ---- per-row attribution accumulation (Shapley attribution, wellflow/explain.py) ----
+//
+// A sampling Shapley run scores the table 1 + repeats x columns times and combines two
+// consecutive passes PER ROW: the column that returned to the row's own value between them is
+// credited with the change of the row's prediction. One grid-stride elementwise launch per pass:
+//   start (all picked columns from the background row): v = (double)p_cur * y_scale + y_shift,
+//          acc[i] += v, sq[i] += v * v             (acc / sq: the base row of the job's tables)
+//   step:  d = ((double)p_cur - (double)p_prev) * y_scale,
+//          acc[i] += d, sq[i] += d * d             (acc / sq: the row of the returned column)
+// and p_prev[i] = p_cur[i] either way. Every operation is a correctly rounded fp64 sub / mul / add,
+// never fused, and cell i is read and written by ONE thread of the launch, with plain vector
+// loads and stores: no atomics, no scratch, no order of additions to depend on, so the tables
+// equal a numpy float64 replay bit for bit. A NaN prediction reaches its own cell only.
+namespace {
+
+__device__ __forceinline__ void attr_cell(float pc, float pp, double y_scale, double y_shift, bool start, double* acc,
+                                          double* sq) {
+#pragma clang fp contract(off)
+  double d;
+  if (start) {
+    const double a = (double)pc * y_scale;
+    d = a + y_shift;
+  } else {
+    const double a = (double)pc - (double)pp;
+    d = a * y_scale;
+  }
+  const double dd = d * d;
+  *acc = *acc + d;
+  *sq = *sq + dd;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void attr_step_kernel(const float* __restrict__ p_cur, float* __restrict__ p_prev,
+                                                        long M, double y_scale, double y_shift,
+                                                        double* __restrict__ acc, double* __restrict__ sq, int start) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < M; i += stride) {
+    const float pc = p_cur[i];
+    const float pp = start ? 0.0f : p_prev[i];  // the start of a repeat does not read the previous pass
+    attr_cell(pc, pp, y_scale, y_shift, start != 0, acc + i, sq + i);
+    p_prev[i] = pc;
+  }
+}
+
+void launch_attr_step(const float* p_cur, float* p_prev, long M, double y_scale, double y_shift, double* acc,
+                      double* sq, bool start, hipStream_t s) {
+  // capped grid, grid-stride over the rest: 8 workgroups per CU of a 256-CU device
+  long blocks = (M + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(attr_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p_cur, p_prev, M, y_scale, y_shift, acc,
+                     sq, start ? 1 : 0);
 }
 
 // ---- grouped prediction sums (response curves, wellflow/response.py) ----

@@ -1,0 +1,354 @@
+"""Shapley attribution: which of the submitted columns moved THIS row's prediction, and by how much?
+
+    python -m wellflow.explain <model> columnNames columnTypes targetColumn storagePath dataPath
+                               [--repeats R=8] [--columns a,b,..] [--std] [--out PATH] [--seed S] [--device D]
+                               [--precision P] [--seq-len T] [--group-col COL] [--batch-size B] [--header]
+
+The prediction, importance and response jobs answer global questions. This one is local: per row
+and per input column a contribution ``phi`` in raw target units which, added to a base value,
+reproduces the row's prediction exactly (local accuracy). The raw column is what is attributed, so
+a categorical column's whole one-hot block moves together.
+
+The rule (sampling Shapley against background rows of the same table). ``K`` picked columns (all
+input columns by default, always kept in the assembly kernel's source order: categorical, then
+continuous), ``R`` repeats. Repeat ``r`` has a background row map ``perm_r [n]`` (row ``i`` is
+paired with row ``perm_r[i]``) and a column order ``order_r`` (a permutation of the picked columns,
+the same for all rows of the repeat).
+
+* pass 0 scores the table as it is: ``p_full``;
+* repeat ``r`` starts with ALL picked columns read through ``perm_r``: ``p_prev``; then, for
+  ``j = 0 .. K-1``, column ``order_r[j]`` returns to the row's own value (columns ``order_r[j+1:]``
+  still come from the background row) and the table is scored again: ``p_cur``. At ``j = K-1``
+  nothing is left permuted, so ``p_cur`` is ``p_full`` and no pass is run: ``1 + R x K`` passes.
+
+All arithmetic is float64 on the fp32 network outputs, never contracted: at the start of a repeat
+``v = p_prev * y_scale + y_shift``, ``base += v``, ``base_sq += v * v``; at each step
+``d = (p_cur - p_prev) * y_scale``, ``phi[k] += d``, ``sq[k] += d * d``, then ``p_prev = p_cur``.
+At the end ``phi /= R``, ``base /= R`` and ``std = sqrt(max(0, sq / R - mean^2))``. Columns that
+were not picked always keep the row's own value. With every one of the ``K!`` orders at one fixed
+``perm`` ``phi`` is the exact Shapley value of the game ``v(S) = f(own values on S, background
+values elsewhere)``; a column the model does not read, and an identity ``perm``, give exactly 0.0.
+
+Draws. ``orders`` come from ``numpy.random.default_rng(seed)`` on the host (``R`` permutations of
+``range(K)``, in repeat order). For mlp, mlp_online and gilbert the row maps come from
+``torch.randperm`` on the scoring device, from a generator seeded with ``seed``, in repeat order
+(as the importance job draws them). For the LSTM the map acts on the SERIES-SORTED row table and
+is by default a cyclic shift ``perm_r[i] = (i + s_r) mod n`` with ``s_r`` in ``[1, n-1]`` drawn
+from the host generator after the orders: a window's background is then another contiguous window,
+not ``T`` unrelated rows. It may straddle a series boundary (the last rows of one series followed
+by the first of the next). Both draws can be injected (``orders``, ``perms``).
+
+On the native path (GPU, bf16) everything stays on the device: the raw columns and the column-set
+masks of all passes are uploaded once; a pass is the assembly kernel's set launch
+(csrc/features.hip: every column of the set read through the permutation) -> the engine's forward
+-> ``attr_step`` (csrc/score.hip), which combines the pass with the previous one per row in the
+fp64 tables. The tables are read once, after the last pass. On the CPU / in fp32 the same rule runs
+in numpy float64 on host-permuted tables: that path is the oracle of the native one. ``gilbert``
+is attributed over whp, choke and glr in host float64: Gilbert's equation is a product of powers of
+the three, so a learned model's attributions have a physical counterpart to be read against.
+"""
+from __future__ import annotations
+
+import csv
+import os
+import sys
+
+import numpy as np
+import torch
+
+from .importance import GILBERT_INPUTS, PermutationImportance
+from .models.gilbert import GilbertModel
+from .predict import Predictor, _numeric_target, scoring_job
+from .scoring import ColumnSet, LstmPass, MlpPass, permuted
+
+
+class ShapleyAttribution(PermutationImportance):
+    """``ShapleyAttribution(predictor, repeats=8, seed=0, piece_rows=0).run(table, columns=None,
+    orders=None, perms=None, target=None)``.
+
+    ``columns``: the picked input columns (default: all); whatever order they are named in, they
+    are kept in the assembly kernel's source order (:meth:`input_columns`), which is the order of
+    ``result["columns"]`` and the order ``orders`` indexes. ``orders``: ints ``[R][K]``, each row a
+    permutation of ``range(K)``. ``perms``: a tensor ``[R][n]`` or a callable ``r -> perm [n]``; n
+    is the table's row count and, for the LSTM, the map acts on the series-sorted row table.
+    ``piece_rows``: rows of the assembled MLP table per piece on the native path (scoring.py)."""
+
+    def __init__(self, predictor: Predictor, repeats: int = 8, seed: int = 0, piece_rows: int = 0):
+        if predictor.name == "cnn":
+            raise ValueError("a Shapley attribution does not apply to cnn: the CNN reads only the target's own "
+                             "history, so there is no input column to attribute a prediction to")
+        if int(repeats) < 1:
+            raise ValueError(f"repeats must be >= 1, got {repeats}")
+        self.pred, self.repeats, self.seed, self.piece_rows = predictor, int(repeats), int(seed), int(piece_rows)
+
+    def _orders(self, orders, rng, R: int, K: int) -> np.ndarray:
+        if orders is None:
+            return np.stack([rng.permutation(K) for _ in range(R)]).astype(np.int64)
+        o = np.asarray(orders)
+        if o.dtype.kind not in "iu":
+            raise TypeError(f"orders must be integers [{R}][{K}], got {o.dtype}")
+        if o.shape != (R, K):
+            raise ValueError(f"orders must be [{R}][{K}] (repeats, picked columns), got {tuple(o.shape)}")
+        for r in range(R):
+            if sorted(o[r].tolist()) != list(range(K)):
+                raise ValueError(f"orders[{r}] = {o[r].tolist()} is not a permutation of 0 .. {K - 1}")
+        return o.astype(np.int64)
+
+    def run(self, table: dict, columns=None, orders=None, perms=None, target: str | None = None) -> dict:
+        """``target``: the target column's name (gilbert only, and only for the reported MSE; a
+        learned model's saved pipeline knows its own). The target column is not required."""
+        pred = self.pred
+        picked = sorted(self._select(columns))  # source order
+        have = self.input_columns()
+        n = len(next(iter(table.values()))) if table else 0
+        if n < 1:
+            raise ValueError("no rows to score")
+        for c, _ in have:
+            if c not in table:
+                raise ValueError(f"the data lacks the input column {c!r}")
+        R, K = self.repeats, len(picked)
+        rng = np.random.default_rng(self.seed)
+        orders = self._orders(orders, rng, R, K)
+        if isinstance(perms, (torch.Tensor, np.ndarray)):
+            perms = torch.as_tensor(perms)
+            if tuple(perms.shape) != (R, n):
+                raise ValueError(f"perms must be [{R}][{n}] (repeats, rows), got {tuple(perms.shape)}")
+        elif perms is not None and not callable(perms):
+            raise TypeError("perms: a tensor [repeats][rows] or a callable repeat -> perm")
+        if pred.name == "gilbert":
+            scorer = _GilbertScorer(pred, table)
+        else:
+            scorer = LearnedScorer(pred, table, self.piece_rows)
+        if scorer.M < 1:
+            raise ValueError(f"no row can be scored: every series is shorter than the window of {pred.seq_len} rows")
+        gen = shifts = None
+        if perms is None and pred.name == "lstm":
+            shifts = rng.integers(1, n, size=R) if n > 1 else np.zeros(R, np.int64)
+        elif perms is None:
+            gen = torch.Generator(device=scorer.perm_device)
+            gen.manual_seed(self.seed)
+        elif isinstance(perms, torch.Tensor):
+            perms = scorer.own_perms(perms)  # one conversion / upload, in front of the pass loop
+        # the column set of every pass that has one, repeat by repeat: all picked columns at the
+        # start, then what is still permuted after step j (nothing after the last: that is p_full)
+        sets = []
+        for r in range(R):
+            sets.append([picked[k] for k in orders[r]])
+            sets += [[picked[k] for k in orders[r, j + 1:]] for j in range(K - 1)]
+        sets = scorer.column_sets(sets, len(have))
+        scorer.begin(K)
+        with torch.no_grad():
+            scorer.full()
+            for r in range(R):
+                if gen is not None:
+                    perm = torch.randperm(n, generator=gen, device=scorer.perm_device, dtype=scorer.perm_dtype)
+                elif shifts is not None:
+                    perm = scorer.own_perms(torch.from_numpy((np.arange(n, dtype=np.int64) + int(shifts[r])) % n))
+                elif callable(perms):
+                    perm = scorer.own_perms(torch.as_tensor(perms(r)))
+                    if perm.shape != (n,):
+                        raise ValueError(f"perms({r}) gave {tuple(perm.shape)}, not [{n}]")
+                else:
+                    perm = perms[r]
+                scorer.step(sets[r * K], perm, K, True)
+                for j in range(K - 1):
+                    scorer.step(sets[r * K + 1 + j], perm, int(orders[r, j]), False)
+                scorer.last(int(orders[r, K - 1]))
+        acc, sq, p_full = scorer.finish()  # float64 [K + 1][M] twice: the one read of the device
+        mean = acc / R
+        std = np.sqrt(np.maximum(0.0, sq / R - mean * mean))  # np.maximum keeps a NaN: shown, not hidden
+        prediction = p_full.astype(np.float64) * scorer.y_scale + scorer.y_shift
+        rows = np.arange(n) if scorer.rows is None else np.asarray(scorer.rows)
+        result = {"model": pred.name, "native": bool(scorer.native), "n": n, "scored": int(scorer.M), "repeats": R,
+                  "columns": [have[k][0] for k in picked], "orders": orders, "rows": rows,
+                  "phi": mean[:K], "std": std[:K], "base": mean[K], "base_std": std[K], "prediction": prediction,
+                  "acc": acc, "sq": sq, "mean_abs": np.abs(mean[:K]).mean(axis=1), "mse": None}
+        tgt = pred.pipe.target if pred.pipe is not None else target
+        y = _numeric_target(table, tgt) if tgt else None
+        if y is not None:
+            d = prediction - y[rows]
+            result["mse"] = float(np.mean(d * d))
+        return result
+
+
+# ---------------------------------------------------------------------- scorers
+class _Scorer:
+    """One table, scored again and again with a set of columns read through a row map; two
+    consecutive passes are combined per row in the float64 tables ``acc`` / ``sq`` ``[K + 1][M]``
+    (row K: the base). Here: the rule in numpy float64, what csrc/score.hip attr_step computes."""
+
+    native = False
+    rows = None
+    perm_device = torch.device("cpu")
+    perm_dtype = torch.int64
+    y_scale, y_shift = 1.0, 0.0
+
+    def own_perms(self, perms: torch.Tensor) -> torch.Tensor:
+        return perms.to(self.perm_device, self.perm_dtype)
+
+    def column_sets(self, sets: list, n_sources: int) -> list:
+        return [ColumnSet(tuple(s)) for s in sets]
+
+    def begin(self, K: int) -> None:
+        self.K = K
+        self.acc = np.zeros((K + 1, self.M), np.float64)
+        self.sq = np.zeros((K + 1, self.M), np.float64)
+
+    def full(self) -> None:
+        self.p_full = np.array(self.score(None, None), copy=True)
+
+    def accumulate(self, p, row: int, start: bool) -> None:
+        pc = np.asarray(p).astype(np.float64)
+        d = pc * self.y_scale + self.y_shift if start else (pc - self.p_prev) * self.y_scale
+        self.acc[row] += d
+        self.sq[row] += d * d
+        self.p_prev = pc
+
+    def step(self, cols, perm, row: int, start: bool) -> None:
+        self.accumulate(self.score(cols, perm), row, start)
+
+    def last(self, row: int) -> None:
+        self.accumulate(self.p_full, row, False)
+
+    def finish(self):
+        return self.acc, self.sq, np.asarray(self.p_full)
+
+
+class _GilbertScorer(_Scorer):
+    """The physical model in host float64 (its predictions are float64 and are used as they are)."""
+
+    def __init__(self, pred, table):
+        self.model = GilbertModel(correlation=pred.extra.get("correlation", "gilbert"))
+        self.cols = {k: np.asarray(table[k], np.float64) for k in GILBERT_INPUTS}
+        self.M = len(self.cols["whp"])
+
+    def score(self, cols, perm):
+        tab = self.cols
+        if cols is not None:
+            pn = perm.numpy()
+            for s in cols.host:
+                tab = permuted(tab, GILBERT_INPUTS[s], pn)
+        return np.asarray(self.model.predict(tab), np.float64)
+
+
+class LearnedScorer(_Scorer):
+    """The MLP and the LSTM: one pass of scoring.py per step, then the per-row accumulation — on
+    the device (csrc/score.hip attr_step) when the native engine scored, else in numpy. LSTM: the
+    columns are permuted over the series-sorted row table; a prediction belongs to its window's
+    last row."""
+
+    def __init__(self, pred, table, piece_rows: int = 0):
+        pipe = pred.pipe
+        if pred.name == "lstm":
+            ps = LstmPass(pred, table, "LSTM attribution scoring")
+        else:
+            ps = MlpPass(pred, table, "MLP attribution scoring", resident=True, piece_rows=piece_rows)
+        self.pred, self.ps, self.M, self.native, self.on_device = pred, ps, ps.M, ps.native, ps.on_device
+        self.rows = ps.rows
+        self.y_scale, self.y_shift = (float(pipe.y_std), float(pipe.y_mean)) if pipe.standardize_target else (1.0, 0.0)
+        if self.on_device:
+            self.perm_device, self.perm_dtype = pred.device, torch.int32
+
+    def column_sets(self, sets, n_sources):
+        if not self.on_device:
+            return super().column_sets(sets, n_sources)
+        from .ops.native import column_masks
+
+        masks = column_masks(sets, n_sources, self.pred.device)  # one upload: [passes][words]
+        return [ColumnSet(tuple(s), masks[i]) for i, s in enumerate(sets)]  # pass i points at its row
+
+    def score(self, cols, perm):
+        return self.ps.score(-1, perm, None, cols)
+
+    def begin(self, K):
+        if not self.native:
+            return super().begin(K)
+        dev = self.pred.device
+        self.K = K
+        self.acc = torch.zeros((K + 1, self.M), dtype=torch.float64, device=dev)
+        self.sq = torch.zeros((K + 1, self.M), dtype=torch.float64, device=dev)
+        self.p_prev = torch.zeros(self.M, dtype=torch.float32, device=dev)
+
+    def full(self):
+        if not self.native:
+            return super().full()
+        self.p_full = self.score(None, None).clone()  # kept: the last step of every repeat reads it
+
+    def accumulate(self, p, row, start):
+        if not self.native:
+            return super().accumulate(p, row, start)
+        from .ops.native import attr_step
+
+        attr_step(p, self.p_prev, self.y_scale, self.y_shift, self.acc, self.sq, row, start)
+
+    def finish(self):
+        self.pred.eng.check_device_errors()
+        if not self.native:
+            return super().finish()
+        return self.acc.cpu().numpy(), self.sq.cpu().numpy(), self.p_full.cpu().numpy()
+
+
+# ---------------------------------------------------------------------- the job
+def _write_csv(path: str, table: dict, names: list, result: dict, with_std: bool) -> None:
+    """The parsed table's columns, echoed, then prediction, base, phi_<column> per picked column
+    (source order) and, with ``with_std``, std_<column>; a row without a prediction (the first
+    T - 1 rows of an LSTM series) gets empty cells. Always with a header; floats as ``repr``.
+    Atomic (tmp + rename)."""
+    n, cols = result["n"], result["columns"]
+    blocks = [("prediction", result["prediction"]), ("base", result["base"])]
+    blocks += [(f"phi_{c}", result["phi"][k]) for k, c in enumerate(cols)]
+    if with_std:
+        blocks += [(f"std_{c}", result["std"][k]) for k, c in enumerate(cols)]
+    pos = np.full(n, -1, np.int64)
+    pos[result["rows"]] = np.arange(len(result["rows"]))
+    echo = [np.asarray(table[c]).astype(str) for c in names]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + ".tmp"
+    with open(tmp, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(list(names) + [b for b, _ in blocks])
+        for i in range(n):
+            m = pos[i]
+            w.writerow([e[i] for e in echo] + [repr(float(v[m])) if m >= 0 else "" for _, v in blocks])
+    os.replace(tmp, path)
+
+
+def run_explain(model: str, argv, log=print) -> dict:
+    def add_arguments(ap):
+        ap.add_argument("--repeats", type=int, default=8, help="sampled column orders / background rows per row (default 8)")
+        ap.add_argument("--columns", default=None, help="comma-separated input columns to attribute to (default: all)")
+        ap.add_argument("--std", action="store_true", help="also write std_<column>: the spread over the repeats")
+
+    ns, cfg, schema, out_path, load_predictor, load_data = scoring_job(
+        "explain", "attribution", "explain", "dataPath", model, argv, add_arguments)
+    if int(os.environ.get("RANK", "0")) != 0:  # one process on one device: rank 0 alone works and writes
+        return {"model": model, "out": out_path, "skipped": True}
+    job = ShapleyAttribution(load_predictor(), repeats=ns.repeats, seed=cfg.seed)
+    table = load_data()
+    columns = [c.strip() for c in ns.columns.split(",") if c.strip()] if ns.columns is not None else None
+    result = job.run(table, columns=columns, target=cfg.target)
+    result["out"] = out_path
+    _write_csv(out_path, table, schema.names, result, ns.std)
+    log("Rows scored: %d" % result["scored"])
+    log("Rows without prediction: %d" % (result["n"] - result["scored"]))
+    log("Mean prediction: %f" % float(np.mean(result["prediction"])))
+    if result["mse"] is not None:
+        log("Scoring MSE: %f" % result["mse"])
+    by = sorted(range(len(result["columns"])), key=lambda k: (0, 0.0) if np.isnan(result["mean_abs"][k])
+                else (1, -result["mean_abs"][k]))  # descending; NaN first (shown, not hidden); ties keep the order
+    for k in by:
+        log("%s: mean |phi| %f" % (result["columns"][k], result["mean_abs"][k]))
+    return result
+
+
+def main(argv=None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if not argv or argv[0] in ("-h", "--help"):
+        print(__doc__)
+        return 0
+    run_explain(argv[0], argv[1:])
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

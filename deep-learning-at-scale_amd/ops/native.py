@@ -97,7 +97,7 @@ class ResidentColumns:
         return (self.F + 7) // 8 * 8 if out_dtype == torch.bfloat16 else self.F
 
     def assemble(self, out_dtype, rows=None, perm=None, perm_col: int = -1, out=None, const_col: int = -1,
-                 const_value=None):
+                 const_value=None, col_set=None):
         """Feature rows ``rows = (a, b)`` (default: all) of the resident table, as
         :func:`assemble_features` builds them. With ``perm`` (int32 device vector of ``b - a``
         indices into ALL N rows) source column ``perm_col`` — in the kernel's source order, the C
@@ -108,6 +108,9 @@ class ResidentColumns:
         source column ``const_col`` is that constant in every output row; it goes through the
         kernel's own block test / standardisation, so the unknown index ``len(labels)`` gives the
         all-zero block. One column is permuted or constant, not both.
+        With ``col_set`` (a row of :func:`column_masks`: int32 [ceil((C + Q) / 32)] on the table's
+        device) EVERY source column of the set is read through ``perm`` (needed; ``perm_col`` stays
+        -1): the set launch of the kernel. Not combined with ``perm_col`` or a constant.
         Everything is refused here, on the host, before a launch; nothing is uploaded."""
         import torch
 
@@ -115,10 +118,26 @@ class ResidentColumns:
         if not 0 <= a < b <= self.N:
             raise ValueError(f"assemble_features: rows [{a}, {b}) outside the table's {self.N} rows")
         perm_col = int(perm_col)
-        if (perm is None) != (perm_col < 0):
+        if col_set is not None:
+            if perm_col >= 0:
+                raise ValueError("assemble_features: a set of permuted columns (col_set) or ONE perm_col, not both")
+            if const_value is not None or int(const_col) >= 0:
+                raise ValueError("assemble_features: a set of permuted columns (col_set) is not combined with a "
+                                 "constant column")
+            if perm is None:
+                raise ValueError("assemble_features: a set of permuted columns (col_set) needs perm")
+            words = (self.C + self.Q + 31) // 32
+            if not isinstance(col_set, torch.Tensor) or col_set.device != self.device:
+                raise ValueError(f"assemble_features: col_set must be a tensor on {self.device}")
+            if col_set.dtype != torch.int32:
+                raise TypeError(f"assemble_features: col_set must be int32 (the mask's 32-bit words), got {col_set.dtype}")
+            if col_set.dim() != 1 or col_set.numel() != words or not col_set.is_contiguous():
+                raise ValueError(f"assemble_features: col_set holds {tuple(col_set.shape)} words for "
+                                 f"{self.C + self.Q} source columns (need {words})")
+        elif (perm is None) != (perm_col < 0):
             raise ValueError("assemble_features: perm and perm_col go together")
         if perm is not None:
-            if not 0 <= perm_col < self.C + self.Q:
+            if col_set is None and not 0 <= perm_col < self.C + self.Q:
                 raise ValueError(f"assemble_features: perm_col {perm_col} outside [0, {self.C + self.Q})")
             if not isinstance(perm, torch.Tensor) or perm.device != self.device:
                 raise ValueError(f"assemble_features: perm must be a tensor on {self.device}")
@@ -149,10 +168,36 @@ class ResidentColumns:
             out = torch.empty((b - a, ld), dtype=out_dtype, device=self.device)
         elif out.shape != (b - a, ld) or out.dtype != out_dtype or out.device != self.device:
             raise ValueError(f"assemble_features: out must be {out_dtype} [{b - a}][{ld}] on {self.device}")
+        if col_set is not None:
+            lib().assemble_features(self.codes, self.cont, self.off, self.size, self.mean, self.std, a, b - a, self.F,
+                                    out, -1, perm, set_mask=col_set)
+            return out
         lib().assemble_features(self.codes, self.cont, self.off, self.size, self.mean, self.std, a, b - a, self.F, out,
                                 perm_col if perm is not None else -1, perm, const_col if const_value is not None else -1,
                                 const_value)
         return out
+
+
+def column_masks(sets, n_sources: int, device=None):
+    """The bitmasks of source-column sets for :meth:`ResidentColumns.assemble` (``col_set``):
+    int32 ``[len(sets)][ceil(n_sources / 32)]``, the bit pattern of 32-bit words in which bit
+    ``s & 31`` of word ``s >> 5`` is source column ``s``. A job builds the masks of all its passes
+    in one call (one upload when ``device`` is given) and a pass points at its row."""
+    import numpy as np
+    import torch
+
+    S = int(n_sources)
+    if S < 1:
+        raise ValueError(f"column_masks: {S} source columns")
+    m = np.zeros((len(sets), (S + 31) // 32), np.uint32)
+    for i, cols in enumerate(sets):
+        for c in cols:
+            c = int(c)
+            if not 0 <= c < S:
+                raise ValueError(f"column_masks: source column {c} outside [0, {S})")
+            m[i, c >> 5] |= np.uint32(1) << np.uint32(c & 31)
+    t = torch.from_numpy(m.view(np.int32))
+    return t if device is None else t.to(device)
 
 
 def err_sums(pred, y, y_scale: float, y_shift: float, out, slot: int, scratch):
@@ -168,6 +213,38 @@ def err_sums(pred, y, y_scale: float, y_shift: float, out, slot: int, scratch):
     if out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != 2 or not 0 <= int(slot) < out.shape[0]:
         raise ValueError(f"err_sums: out must be float64 [S][2] with slot {slot} inside it")
     lib().err_sums(pred, y, float(y_scale), float(y_shift), out, int(slot), scratch)
+
+
+def attr_step(p_cur, p_prev, y_scale: float, y_shift: float, acc, sq, row: int, start: bool = False):
+    """One step of a sampling Shapley run (csrc/score.hip): in row ``row`` of the fp64 tables
+    ``acc`` / ``sq`` ``[K + 1][M]``, ``d = (p_cur - p_prev) * y_scale`` — with ``start``
+    ``d = p_cur * y_scale + y_shift`` — then ``acc += d``, ``sq += d * d`` (uncontracted fp64, one
+    thread per cell: a numpy float64 replay bit for bit), and ``p_prev = p_cur``. ``p_cur`` /
+    ``p_prev``: distinct fp32 device vectors [M]. Stream-ordered; nothing comes back to the host."""
+    import torch
+
+    for name, t in (("p_cur", p_cur), ("p_prev", p_prev)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"attr_step: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if p_cur.dim() != 1 or p_cur.shape != p_prev.shape or p_cur.numel() < 1:
+        raise ValueError(f"attr_step: p_cur {tuple(p_cur.shape)} and p_prev {tuple(p_prev.shape)} must be equal, "
+                         f"non-empty vectors")
+    if not p_cur.is_contiguous() or not p_prev.is_contiguous():
+        raise ValueError("attr_step: p_cur / p_prev must be contiguous")
+    M = p_cur.numel()
+    for name, t in (("acc", acc), ("sq", sq)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError(f"attr_step: {name} must be a float64 tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 2 or t.shape[1] != M or not t.is_contiguous():
+            raise ValueError(f"attr_step: {name} must be contiguous float64 [K + 1][{M}], got {tuple(t.shape)}")
+    if acc.shape != sq.shape:
+        raise ValueError(f"attr_step: acc {tuple(acc.shape)} and sq {tuple(sq.shape)} differ")
+    if not (p_cur.device == p_prev.device == acc.device == sq.device) or p_cur.device.type != "cuda":
+        raise ValueError(f"attr_step: the tensors must be on one GPU, got {p_cur.device}, {p_prev.device}, "
+                         f"{acc.device}, {sq.device}")
+    if not 0 <= int(row) < acc.shape[0]:
+        raise ValueError(f"attr_step: row {row} outside [0, {acc.shape[0]})")
+    lib().attr_step(p_cur, p_prev, float(y_scale), float(y_shift), acc, sq, int(row), bool(start))
 
 
 ERR_SUMS_SCRATCH = 2 * 256 + 1  # csrc/kernels.h kErrSumsScratch: a partial pair per workgroup + the ticket

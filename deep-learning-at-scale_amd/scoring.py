@@ -1,5 +1,6 @@
 """One scoring pass over a table: what the prediction job (predict.py) runs once and the
-permutation-importance job (importance.py) runs ``1 + columns x repeats`` times.
+permutation-importance job (importance.py) runs ``1 + columns x repeats`` times (the response and
+attribution jobs, response.py and explain.py, run it in the same way).
 
 A pass is built once per table from a :class:`~wellflow.predict.Predictor`. It owns the engine and
 its batch, the piece size, the preallocated device buffers and the choice between the three input
@@ -15,7 +16,8 @@ routes:
 ``score(k, perm)`` returns the network outputs as fp32 ``[M]``: a device tensor (the pass's own
 buffer) on the native routes, a numpy array from the oracle. Source column ``k`` is read through
 the permutation ``perm`` (importance.py) or, with ``const``, set to one constant in every row
-(response.py); without either the table is scored as it is.
+(response.py); without either the table is scored as it is. ``score(perm=perm, cols=set)`` reads
+every source column of a :class:`ColumnSet` through ``perm`` (explain.py).
 """
 from __future__ import annotations
 
@@ -40,6 +42,13 @@ def permuted(table: dict, col: str, perm) -> dict:
 # same value as a one-element device tensor (the int32 label code / the float32 value: an element
 # of a grid that was uploaded once), what the device assembly reads.
 Constant = collections.namedtuple("Constant", ["host", "dev"], defaults=[None])
+
+
+# A SET of source columns read through one permutation. ``host``: the source-column indices (the
+# kernel's source order), what the host routes permute one by one; ``dev``: the set's bitmask, a row
+# of ``ops.native.column_masks`` on the device (a job uploads the masks of all its passes once and
+# a pass points at its row), what the device assembly reads.
+ColumnSet = collections.namedtuple("ColumnSet", ["host", "dev"], defaults=[None])
 
 
 def constant(table: dict, col: str, value) -> dict:
@@ -77,8 +86,16 @@ class _Pass:
         pipe = self.pipe
         return ResidentColumns(codes, cont, *pipe.block_spec(), *pipe.scale(), self.pred.n_features, self.pred.device)
 
-    def _features(self, k: int, perm, const=None) -> np.ndarray:
-        """The host pipeline's rows, source column ``k`` read through ``perm`` or set to ``const``."""
+    def _features(self, k: int, perm, const=None, cols=None) -> np.ndarray:
+        """The host pipeline's rows, source column ``k`` read through ``perm`` or set to ``const``,
+        or every source column of ``cols`` (a :class:`ColumnSet`) read through ``perm``."""
+        if cols is not None:
+            if k >= 0 or const is not None:
+                raise ValueError("a set of permuted columns is not combined with one permuted or constant column")
+            tab, pn = self.table, torch.as_tensor(perm).cpu().numpy()
+            for s in cols.host:
+                tab = permuted(tab, self.names[s], pn)
+            return self.pipe.features(tab)
         if k >= 0 and const is not None:
             return self.pipe.features(constant(self.table, self.names[k], const.host))
         tab = self.table if k < 0 else permuted(self.table, self.names[k], torch.as_tensor(perm).cpu().numpy())
@@ -87,15 +104,24 @@ class _Pass:
     def _input_format(self, X: torch.Tensor) -> torch.Tensor:
         return X
 
-    def assemble(self, a: int, b: int, k: int = -1, perm=None, host=None, const=None) -> torch.Tensor:
+    def assemble(self, a: int, b: int, k: int = -1, perm=None, host=None, const=None, cols=None) -> torch.Tensor:
         """Rows [a, b) of the table as engine input, in the pass's piece buffer. Device assembly:
         source column ``k`` (or -1) is read through ``perm`` (int32 device vector over ALL rows;
         resident columns only) or set to ``const.dev`` (a :class:`Constant`; resident columns
-        only). ``host``: the host-built rows of the whole table instead (host assembly with the
-        native engine)."""
+        only); or every source column of ``cols.dev`` (a :class:`ColumnSet`; resident columns
+        only) is read through ``perm``. ``host``: the host-built rows of the whole table instead
+        (host assembly with the native engine)."""
         X = self.X[: b - a]
         if host is not None:
             X.copy_(self._input_format(torch.from_numpy(host[a:b])))
+        elif cols is not None:
+            if self.res is None:
+                raise ValueError("a pass with a set of permuted columns reads resident columns (resident=True)")
+            if k >= 0 or const is not None:
+                raise ValueError("a set of permuted columns is not combined with one permuted or constant column")
+            if perm is None:
+                raise ValueError("a set of permuted columns needs perm")
+            self.res.assemble(self.dtype, rows=(a, b), perm=perm[a:b], col_set=cols.dev, out=X)
         elif k >= 0 and const is not None:
             if self.res is None:
                 raise ValueError("a constant pass reads resident columns (resident=True)")
@@ -108,14 +134,15 @@ class _Pass:
             self._resident(self.codes[:, a:b], self.cont[:, a:b]).assemble(self.dtype, out=X)
         return X
 
-    def score(self, k: int = -1, perm=None, const=None):
+    def score(self, k: int = -1, perm=None, const=None, cols=None):
         """Network outputs fp32 [M], source column ``k`` (or -1: none) read through ``perm`` or,
-        with ``const`` (a :class:`Constant`), set to that value in every row."""
+        with ``const`` (a :class:`Constant`), set to that value in every row; with ``cols`` (a
+        :class:`ColumnSet`) every source column of the set is read through ``perm``."""
         if not self.native:
-            return self._score_host(self._features(k, perm, const))
-        host = None if self.on_device else self._features(k, perm, const)
+            return self._score_host(self._features(k, perm, const, cols))
+        host = None if self.on_device else self._features(k, perm, const, cols)
         for a, b in self.pieces:
-            self.forward(self.assemble(a, b, k, perm, host, const), a)
+            self.forward(self.assemble(a, b, k, perm, host, const, cols), a)
         return self.p
 
 

@@ -12,6 +12,10 @@ ranks the input columns of that ``.mdl`` by permutation importance (wellflow/imp
 ``python -m wellflow.submit response <model> columnNames columnTypes targetColumn storagePath dataPath --columns a[,b..]``
 sweeps one input column at a time over a grid and writes the mean prediction per value, overall and
 per ``--by`` group: the model's response curves (wellflow/response.py).
+
+``python -m wellflow.submit explain <model> columnNames columnTypes targetColumn storagePath dataPath``
+attributes every row's prediction to the input columns: per-row Shapley contributions in raw target
+units that, added to a base value, give the prediction (wellflow/explain.py).
 """
 import sys
 
@@ -35,6 +39,10 @@ def main(argv=None) -> int:
         from .response import main as response_main
 
         return response_main(argv[1:])
+    if argv[0] == "explain":  # per-row Shapley attribution of a saved .mdl's predictions to its input columns
+        from .explain import main as explain_main
+
+        return explain_main(argv[1:])
     run_job(argv[0], argv[1:])
     return 0
 
