@@ -375,10 +375,12 @@ class NativeMLP:
                            f"{self.Fp} padded features need the 128-row one-launch step (a path A/B switched it off)",
                            f"F={self.F} hidden={self.hidden} B={B}")
             return False
-        if self.loss_kind != "mse" and (self.red is None or not self.step_fused):
-            # the clipped MAE is fused into the one-launch step only (not the kernel pair)
+        if self.loss_kind != "mse" and (self.red is None or not self.step_fused or self.dw2_gemm):
+            # the clipped MAE is fused into the one-launch step only (not the kernel pair, which
+            # dw2_gemm selects too: its dy is the MSE gradient)
             note_slow_path("MLP", "training step runs the multi-launch path",
-                           f"loss {self.loss_kind!r} needs the one-launch step (WELLFLOW_MLP_SPREAD=0 set)",
+                           f"loss {self.loss_kind!r} needs the one-launch step (WELLFLOW_MLP_SPREAD=0 or a path "
+                           f"A/B switched it off)",
                            f"F={self.F} hidden={self.hidden} B={B}")
             return False
         return self.recompute_h1 and self.fused and self.fused_bwd and self.mask_h2
@@ -421,6 +423,10 @@ class NativeMLP:
         why = self.small_steps_reason(B, opt)
         if why is not None:
             raise RuntimeError(f"NativeMLP.fused_steps: {why}")
+        if X.dim() != 2 or X.shape[1] != self.Fp:
+            # the launcher indexes rows with stride Fp: an [N][F] tensor with F < Fp would be misread
+            raise RuntimeError(f"NativeMLP.fused_steps: X must be [N][{self.Fp}] (to_input_format), got "
+                               f"{tuple(X.shape)}")
         if getattr(self, "_small_scr", None) is None:
             self._small_scr = torch.zeros(self._C.mlp_small_scratch_floats(), device=self.device)
             self._small_sync = torch.zeros(4, dtype=torch.int32, device=self.device)
