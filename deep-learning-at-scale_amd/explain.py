@@ -49,20 +49,17 @@ the three, so a learned model's attributions have a physical counterpart to be r
 """
 from __future__ import annotations
 
-import csv
-import os
 import sys
 
 import numpy as np
 import torch
 
-from .importance import GILBERT_INPUTS, PermutationImportance
-from .models.gilbert import GilbertModel
 from .predict import Predictor, _numeric_target, scoring_job
-from .scoring import ColumnSet, LstmPass, MlpPass, permuted
+from .scoring import PermutedSet
+from .whatif import Permutations, comma_list, input_columns, other_rank, scorer_for, select_columns, table_rows, write_csv
 
 
-class ShapleyAttribution(PermutationImportance):
+class ShapleyAttribution:
     """``ShapleyAttribution(predictor, repeats=8, seed=0, piece_rows=0).run(table, columns=None,
     orders=None, perms=None, target=None)``.
 
@@ -81,6 +78,10 @@ class ShapleyAttribution(PermutationImportance):
             raise ValueError(f"repeats must be >= 1, got {repeats}")
         self.pred, self.repeats, self.seed, self.piece_rows = predictor, int(repeats), int(seed), int(piece_rows)
 
+    def input_columns(self) -> list:
+        """[(name, kind)] in the assembly kernel's source order (categorical, then continuous)."""
+        return input_columns(self.pred)
+
     def _orders(self, orders, rng, R: int, K: int) -> np.ndarray:
         if orders is None:
             return np.stack([rng.permutation(K) for _ in range(R)]).astype(np.int64)
@@ -98,63 +99,40 @@ class ShapleyAttribution(PermutationImportance):
         """``target``: the target column's name (gilbert only, and only for the reported MSE; a
         learned model's saved pipeline knows its own). The target column is not required."""
         pred = self.pred
-        picked = sorted(self._select(columns))  # source order
+        picked = sorted(select_columns(pred, columns, "no column to permute"))  # source order
         have = self.input_columns()
-        n = len(next(iter(table.values()))) if table else 0
-        if n < 1:
-            raise ValueError("no rows to score")
-        for c, _ in have:
-            if c not in table:
-                raise ValueError(f"the data lacks the input column {c!r}")
+        n = table_rows(pred, table)
         R, K = self.repeats, len(picked)
         rng = np.random.default_rng(self.seed)
         orders = self._orders(orders, rng, R, K)
-        if isinstance(perms, (torch.Tensor, np.ndarray)):
-            perms = torch.as_tensor(perms)
-            if tuple(perms.shape) != (R, n):
-                raise ValueError(f"perms must be [{R}][{n}] (repeats, rows), got {tuple(perms.shape)}")
-        elif perms is not None and not callable(perms):
-            raise TypeError("perms: a tensor [repeats][rows] or a callable repeat -> perm")
-        if pred.name == "gilbert":
-            scorer = _GilbertScorer(pred, table)
-        else:
-            scorer = LearnedScorer(pred, table, self.piece_rows)
-        if scorer.M < 1:
-            raise ValueError(f"no row can be scored: every series is shorter than the window of {pred.seq_len} rows")
-        gen = shifts = None
-        if perms is None and pred.name == "lstm":
+        cyclic = perms is None and pred.name == "lstm"
+        perms = Permutations(perms, (R, n), "repeats, rows", "repeat")
+        scorer = scorer_for(pred, table, "attribution", self.piece_rows)
+        if cyclic:
             shifts = rng.integers(1, n, size=R) if n > 1 else np.zeros(R, np.int64)
-        elif perms is None:
-            gen = torch.Generator(device=scorer.perm_device)
-            gen.manual_seed(self.seed)
-        elif isinstance(perms, torch.Tensor):
-            perms = scorer.own_perms(perms)  # one conversion / upload, in front of the pass loop
+        else:
+            perms.bind(scorer, self.seed)
         # the column set of every pass that has one, repeat by repeat: all picked columns at the
         # start, then what is still permuted after step j (nothing after the last: that is p_full)
         sets = []
         for r in range(R):
             sets.append([picked[k] for k in orders[r]])
             sets += [[picked[k] for k in orders[r, j + 1:]] for j in range(K - 1)]
-        sets = scorer.column_sets(sets, len(have))
-        scorer.begin(K)
+        att = Attribution(scorer)
+        sets = att.column_sets(sets, len(have))
+        att.begin(K)
         with torch.no_grad():
-            scorer.full()
+            att.full()
             for r in range(R):
-                if gen is not None:
-                    perm = torch.randperm(n, generator=gen, device=scorer.perm_device, dtype=scorer.perm_dtype)
-                elif shifts is not None:
+                if cyclic:
                     perm = scorer.own_perms(torch.from_numpy((np.arange(n, dtype=np.int64) + int(shifts[r])) % n))
-                elif callable(perms):
-                    perm = scorer.own_perms(torch.as_tensor(perms(r)))
-                    if perm.shape != (n,):
-                        raise ValueError(f"perms({r}) gave {tuple(perm.shape)}, not [{n}]")
                 else:
-                    perm = perms[r]
-                scorer.step(sets[r * K], perm, K, True)
+                    perm = perms.draw((r,), (r,))
+                att.step(sets[r * K], perm, K, True)
                 for j in range(K - 1):
-                    scorer.step(sets[r * K + 1 + j], perm, int(orders[r, j]), False)
-                scorer.last(int(orders[r, K - 1]))
-        acc, sq, p_full = scorer.finish()  # float64 [K + 1][M] twice: the one read of the device
+                    att.step(sets[r * K + 1 + j], perm, int(orders[r, j]), False)
+                att.last(int(orders[r, K - 1]))
+        acc, sq, p_full = att.finish()  # float64 [K + 1][M] twice: the one read of the device
         mean = acc / R
         std = np.sqrt(np.maximum(0.0, sq / R - mean * mean))  # np.maximum keeps a NaN: shown, not hidden
         prediction = p_full.astype(np.float64) * scorer.y_scale + scorer.y_shift
@@ -171,121 +149,65 @@ class ShapleyAttribution(PermutationImportance):
         return result
 
 
-# ---------------------------------------------------------------------- scorers
-class _Scorer:
-    """One table, scored again and again with a set of columns read through a row map; two
-    consecutive passes are combined per row in the float64 tables ``acc`` / ``sq`` ``[K + 1][M]``
-    (row K: the base). Here: the rule in numpy float64, what csrc/score.hip attr_step computes."""
+# ---------------------------------------------------------------------- the reduction
+class Attribution:
+    """Two consecutive passes of the scorer (whatif.py) are combined per row in the float64 tables
+    ``acc`` / ``sq`` ``[K + 1][M]`` (row K: the base): on the device (csrc/score.hip attr_step)
+    when the NATIVE engine scored (the predictions are there, whichever side assembled), else the
+    same rule in numpy float64."""
 
-    native = False
-    rows = None
-    perm_device = torch.device("cpu")
-    perm_dtype = torch.int64
-    y_scale, y_shift = 1.0, 0.0
-
-    def own_perms(self, perms: torch.Tensor) -> torch.Tensor:
-        return perms.to(self.perm_device, self.perm_dtype)
+    def __init__(self, scorer):
+        self.scorer, self.device = scorer, scorer.native
 
     def column_sets(self, sets: list, n_sources: int) -> list:
-        return [ColumnSet(tuple(s)) for s in sets]
+        """(host, dev) of every set: the indices and, for the device assembly, the row of ONE
+        upload of all masks ``[passes][words]`` that the pass points at."""
+        if not self.scorer.on_device:
+            return [(tuple(s), None) for s in sets]
+        from .ops.native import column_masks
+
+        masks = column_masks(sets, n_sources, self.scorer.pred.device)
+        return [(tuple(s), masks[i]) for i, s in enumerate(sets)]
 
     def begin(self, K: int) -> None:
-        self.K = K
-        self.acc = np.zeros((K + 1, self.M), np.float64)
-        self.sq = np.zeros((K + 1, self.M), np.float64)
+        M = self.scorer.M
+        if self.device:
+            dev = self.scorer.pred.device
+            self.acc = torch.zeros((K + 1, M), dtype=torch.float64, device=dev)
+            self.sq = torch.zeros((K + 1, M), dtype=torch.float64, device=dev)
+            self.p_prev = torch.zeros(M, dtype=torch.float32, device=dev)
+        else:
+            self.acc = np.zeros((K + 1, M), np.float64)
+            self.sq = np.zeros((K + 1, M), np.float64)
 
     def full(self) -> None:
-        self.p_full = np.array(self.score(None, None), copy=True)
+        p = self.scorer.predict()  # kept (a copy): the last step of every repeat reads it
+        self.p_full = p.clone() if self.device else np.array(p, copy=True)
 
     def accumulate(self, p, row: int, start: bool) -> None:
-        pc = np.asarray(p).astype(np.float64)
-        d = pc * self.y_scale + self.y_shift if start else (pc - self.p_prev) * self.y_scale
-        self.acc[row] += d
-        self.sq[row] += d * d
-        self.p_prev = pc
+        s = self.scorer
+        if self.device:
+            from .ops.native import attr_step
 
-    def step(self, cols, perm, row: int, start: bool) -> None:
-        self.accumulate(self.score(cols, perm), row, start)
+            attr_step(p, self.p_prev, s.y_scale, s.y_shift, self.acc, self.sq, row, start)
+        else:
+            pc = np.asarray(p).astype(np.float64)
+            d = pc * s.y_scale + s.y_shift if start else (pc - self.p_prev) * s.y_scale
+            self.acc[row] += d
+            self.sq[row] += d * d
+            self.p_prev = pc
+
+    def step(self, cols: tuple, perm, row: int, start: bool) -> None:
+        self.accumulate(self.scorer.predict(PermutedSet(*cols, perm)), row, start)
 
     def last(self, row: int) -> None:
         self.accumulate(self.p_full, row, False)
 
     def finish(self):
+        self.scorer.check_device_errors()
+        if self.device:
+            return self.acc.cpu().numpy(), self.sq.cpu().numpy(), self.p_full.cpu().numpy()
         return self.acc, self.sq, np.asarray(self.p_full)
-
-
-class _GilbertScorer(_Scorer):
-    """The physical model in host float64 (its predictions are float64 and are used as they are)."""
-
-    def __init__(self, pred, table):
-        self.model = GilbertModel(correlation=pred.extra.get("correlation", "gilbert"))
-        self.cols = {k: np.asarray(table[k], np.float64) for k in GILBERT_INPUTS}
-        self.M = len(self.cols["whp"])
-
-    def score(self, cols, perm):
-        tab = self.cols
-        if cols is not None:
-            pn = perm.numpy()
-            for s in cols.host:
-                tab = permuted(tab, GILBERT_INPUTS[s], pn)
-        return np.asarray(self.model.predict(tab), np.float64)
-
-
-class LearnedScorer(_Scorer):
-    """The MLP and the LSTM: one pass of scoring.py per step, then the per-row accumulation — on
-    the device (csrc/score.hip attr_step) when the native engine scored, else in numpy. LSTM: the
-    columns are permuted over the series-sorted row table; a prediction belongs to its window's
-    last row."""
-
-    def __init__(self, pred, table, piece_rows: int = 0):
-        pipe = pred.pipe
-        if pred.name == "lstm":
-            ps = LstmPass(pred, table, "LSTM attribution scoring")
-        else:
-            ps = MlpPass(pred, table, "MLP attribution scoring", resident=True, piece_rows=piece_rows)
-        self.pred, self.ps, self.M, self.native, self.on_device = pred, ps, ps.M, ps.native, ps.on_device
-        self.rows = ps.rows
-        self.y_scale, self.y_shift = (float(pipe.y_std), float(pipe.y_mean)) if pipe.standardize_target else (1.0, 0.0)
-        if self.on_device:
-            self.perm_device, self.perm_dtype = pred.device, torch.int32
-
-    def column_sets(self, sets, n_sources):
-        if not self.on_device:
-            return super().column_sets(sets, n_sources)
-        from .ops.native import column_masks
-
-        masks = column_masks(sets, n_sources, self.pred.device)  # one upload: [passes][words]
-        return [ColumnSet(tuple(s), masks[i]) for i, s in enumerate(sets)]  # pass i points at its row
-
-    def score(self, cols, perm):
-        return self.ps.score(-1, perm, None, cols)
-
-    def begin(self, K):
-        if not self.native:
-            return super().begin(K)
-        dev = self.pred.device
-        self.K = K
-        self.acc = torch.zeros((K + 1, self.M), dtype=torch.float64, device=dev)
-        self.sq = torch.zeros((K + 1, self.M), dtype=torch.float64, device=dev)
-        self.p_prev = torch.zeros(self.M, dtype=torch.float32, device=dev)
-
-    def full(self):
-        if not self.native:
-            return super().full()
-        self.p_full = self.score(None, None).clone()  # kept: the last step of every repeat reads it
-
-    def accumulate(self, p, row, start):
-        if not self.native:
-            return super().accumulate(p, row, start)
-        from .ops.native import attr_step
-
-        attr_step(p, self.p_prev, self.y_scale, self.y_shift, self.acc, self.sq, row, start)
-
-    def finish(self):
-        self.pred.eng.check_device_errors()
-        if not self.native:
-            return super().finish()
-        return self.acc.cpu().numpy(), self.sq.cpu().numpy(), self.p_full.cpu().numpy()
 
 
 # ---------------------------------------------------------------------- the job
@@ -302,15 +224,8 @@ def _write_csv(path: str, table: dict, names: list, result: dict, with_std: bool
     pos = np.full(n, -1, np.int64)
     pos[result["rows"]] = np.arange(len(result["rows"]))
     echo = [np.asarray(table[c]).astype(str) for c in names]
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = path + ".tmp"
-    with open(tmp, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(list(names) + [b for b, _ in blocks])
-        for i in range(n):
-            m = pos[i]
-            w.writerow([e[i] for e in echo] + [repr(float(v[m])) if m >= 0 else "" for _, v in blocks])
-    os.replace(tmp, path)
+    write_csv(path, list(names) + [b for b, _ in blocks],
+              ([e[i] for e in echo] + [repr(float(v[m])) if m >= 0 else "" for _, v in blocks] for i, m in enumerate(pos)))
 
 
 def run_explain(model: str, argv, log=print) -> dict:
@@ -321,12 +236,11 @@ def run_explain(model: str, argv, log=print) -> dict:
 
     ns, cfg, schema, out_path, load_predictor, load_data = scoring_job(
         "explain", "attribution", "explain", "dataPath", model, argv, add_arguments)
-    if int(os.environ.get("RANK", "0")) != 0:  # one process on one device: rank 0 alone works and writes
-        return {"model": model, "out": out_path, "skipped": True}
+    if skipped := other_rank(model, out_path):
+        return skipped
     job = ShapleyAttribution(load_predictor(), repeats=ns.repeats, seed=cfg.seed)
     table = load_data()
-    columns = [c.strip() for c in ns.columns.split(",") if c.strip()] if ns.columns is not None else None
-    result = job.run(table, columns=columns, target=cfg.target)
+    result = job.run(table, columns=comma_list(ns.columns), target=cfg.target)
     result["out"] = out_path
     _write_csv(out_path, table, schema.names, result, ns.std)
     log("Rows scored: %d" % result["scored"])

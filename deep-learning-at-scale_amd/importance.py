@@ -23,18 +23,15 @@ Error of a pass, in raw target units, all in float64 (p: the network's output, y
 """
 from __future__ import annotations
 
-import csv
-import os
 import sys
 
 import numpy as np
 import torch
 
-from .models.gilbert import GilbertModel
 from .predict import Predictor, _numeric_target, scoring_job
-from .scoring import LstmPass, MlpPass, permuted
+from .scoring import PermutedColumn
+from .whatif import Permutations, comma_list, input_columns, other_rank, scorer_for, select_columns, table_rows, write_csv
 
-GILBERT_INPUTS = ("whp", "choke", "glr")
 CSV_COLUMNS = ("column", "kind", "baseline_mse", "permuted_mse_mean", "permuted_mse_std", "importance", "ratio",
                "baseline_mae", "permuted_mae_mean")
 
@@ -59,35 +56,13 @@ class PermutationImportance:
             raise ValueError(f"repeats must be >= 1, got {repeats}")
         self.pred, self.repeats, self.seed, self.piece_rows = predictor, int(repeats), int(seed), int(piece_rows)
 
-    # ------------------------------------------------------------------ columns
     def input_columns(self) -> list:
         """[(name, kind)] of every column that can be permuted, in the assembly kernel's source
         order: the categorical columns (saved indexer order), then the continuous ones."""
-        if self.pred.name == "gilbert":
-            return [(c, "continuous") for c in GILBERT_INPUTS]
-        pipe = self.pred.pipe
-        return [(ix.column, "categorical") for ix in pipe.indexers] + [(c, "continuous") for c in pipe.continuous]
+        return input_columns(self.pred)
 
-    def _select(self, columns):
-        have = self.input_columns()
-        if columns is None:
-            return list(range(len(have)))
-        names = [c for c, _ in have]
-        picked = []
-        for c in columns:
-            if c not in names:
-                what = ("gilbert reads only " + ", ".join(GILBERT_INPUTS)) if self.pred.name == "gilbert" else \
-                    f"the model's input columns are {names}"
-                raise ValueError(f"unknown column {c!r}: {what}")
-            if names.index(c) in picked:
-                raise ValueError(f"column {c!r} listed twice")
-            picked.append(names.index(c))
-        if not picked:
-            raise ValueError("no column to permute")
-        return picked
-
-    def _target(self, table: dict) -> np.ndarray:
-        tgt = self.pred.pipe.target if self.pred.pipe is not None else self.target
+    def _target(self, table: dict, target) -> np.ndarray:
+        tgt = self.pred.pipe.target if self.pred.pipe is not None else target
         if not tgt:
             raise ValueError("gilbert: name the target column (run(table, target=...))")
         if tgt not in table:
@@ -101,51 +76,23 @@ class PermutationImportance:
     def run(self, table: dict, columns=None, perms=None, target: str | None = None) -> dict:
         """``target``: the target column's name (gilbert only; a learned model's saved pipeline
         knows its own)."""
-        self.target = target
         pred = self.pred
-        picked = self._select(columns)
+        picked = select_columns(pred, columns, "no column to permute")
         have = self.input_columns()
-        n = len(next(iter(table.values()))) if table else 0
-        if n < 1:
-            raise ValueError("no rows to score")
-        for c, _ in have:
-            if c not in table:
-                raise ValueError(f"the data lacks the input column {c!r}")
-        y = self._target(table)
+        n = table_rows(pred, table)
+        y = self._target(table, target)
         R, K = self.repeats, len(picked)
-        if isinstance(perms, torch.Tensor) or isinstance(perms, np.ndarray):
-            perms = torch.as_tensor(perms)
-            if tuple(perms.shape) != (K, R, n):
-                raise ValueError(f"perms must be [{K}][{R}][{n}] (columns, repeats, rows), got {tuple(perms.shape)}")
-        elif perms is not None and not callable(perms):
-            raise TypeError("perms: a tensor [columns][repeats][rows] or a callable (column, repeat) -> perm")
-        if pred.name == "gilbert":
-            scorer = _GilbertScorer(pred, table, y)
-        else:
-            scorer = LearnedScorer(pred, table, y, self.piece_rows)
-        if scorer.M < 1:
-            raise ValueError(f"no row can be scored: every series is shorter than the window of {pred.seq_len} rows")
-        gen = None
-        if perms is None:
-            gen = torch.Generator(device=scorer.perm_device)
-            gen.manual_seed(self.seed)
-        elif isinstance(perms, torch.Tensor):
-            perms = scorer.own_perms(perms)  # one conversion / upload, in front of the pass loop
-        scorer.begin(1 + K * R)
+        perms = Permutations(perms, (K, R, n), "columns, repeats, rows", "(column, repeat)")
+        scorer = scorer_for(pred, table, "importance", self.piece_rows)
+        perms.bind(scorer, self.seed)
+        err = ErrorSums(scorer, y)
+        err.begin(1 + K * R)
         with torch.no_grad():
-            scorer.score(0, -1, None)
+            err.score(0)
             for i, k in enumerate(picked):
                 for r in range(R):
-                    if gen is not None:
-                        perm = torch.randperm(n, generator=gen, device=scorer.perm_device, dtype=scorer.perm_dtype)
-                    elif callable(perms):
-                        perm = scorer.own_perms(torch.as_tensor(perms(have[k][0], r)))
-                        if perm.shape != (n,):
-                            raise ValueError(f"perms({have[k][0]!r}, {r}) gave {tuple(perm.shape)}, not [{n}]")
-                    else:
-                        perm = perms[i, r]
-                    scorer.score(1 + i * R + r, k, perm)
-        sums = scorer.finish()  # float64 [1 + K * R][2]: the one read of the device
+                    err.score(1 + i * R + r, PermutedColumn(k, perms.draw((i, r), (have[k][0], r))))
+        sums = err.finish()  # float64 [1 + K * R][2]: the one read of the device
         M = scorer.M
         base_mse, base_mae = sums[0, 0] / M, sums[0, 1] / M
         rows = []
@@ -167,100 +114,62 @@ class PermutationImportance:
                 "baseline_mse": float(base_mse), "baseline_mae": float(base_mae), "sums": sums, "importance": rows}
 
 
-# ---------------------------------------------------------------------- scorers
+# ---------------------------------------------------------------------- the reduction
 def _err_sums_host(p, y64, y_scale: float, y_shift: float):
     """The error formula in numpy float64 (what csrc/score.hip computes on the device)."""
     d = np.asarray(p).astype(np.float64) * y_scale + y_shift - y64
     return float(np.sum(d * d)), float(np.sum(np.abs(d)))
 
 
-class _Scorer:
-    """One table, scored again and again with one column permuted. ``score(slot, k, perm)``
-    leaves the pass's {sum d^2, sum |d|} in ``slot``; ``finish()`` returns them all."""
+class ErrorSums:
+    """``score(slot, edit)`` scores the edited table (whatif.py) and leaves the pass's
+    {sum d^2, sum |d|} in ``slot``; ``finish()`` returns them all. The sums are formed on the device
+    (csrc/score.hip) when the pass ASSEMBLES there (the target is uploaded next to the raw
+    columns), else in numpy. A learned model is scored against the target in the kernel's format,
+    fp32, on both paths, at each prediction's row (LSTM: its window's last row)."""
 
-    native = False
-    perm_device = torch.device("cpu")
-    perm_dtype = torch.int64
-
-    def own_perms(self, perms: torch.Tensor) -> torch.Tensor:
-        return perms.to(self.perm_device, self.perm_dtype)
-
-    def begin(self, passes: int) -> None:
-        self.sums = np.zeros((passes, 2), np.float64)
-
-    def finish(self) -> np.ndarray:
-        return self.sums
-
-
-class _GilbertScorer(_Scorer):
-    def __init__(self, pred, table, y64):
-        self.model = GilbertModel(correlation=pred.extra.get("correlation", "gilbert"))
-        self.cols = {k: np.asarray(table[k], np.float64) for k in GILBERT_INPUTS}
-        self.y, self.M = y64, len(y64)
-
-    def score(self, slot, k, perm):
-        cols = self.cols if k < 0 else permuted(self.cols, GILBERT_INPUTS[k], perm.numpy())
-        self.sums[slot] = _err_sums_host(self.model.predict(cols), self.y, 1.0, 0.0)
-
-
-class LearnedScorer(_Scorer):
-    """The MLP and the LSTM: one pass of scoring.py per ``score``, then the error sums — on the
-    device (csrc/score.hip) when the pass assembles there, else in numpy. LSTM: the column is
-    permuted over the series-sorted row table; target: the raw target at each window's last row."""
-
-    def __init__(self, pred, table, y64, piece_rows: int = 0):
-        pipe = pred.pipe
-        if pred.name == "lstm":
-            ps = LstmPass(pred, table, "LSTM importance scoring")
-        else:
-            ps = MlpPass(pred, table, "MLP importance scoring", resident=True, piece_rows=piece_rows)
-        self.pred, self.ps, self.M, self.native, self.on_device = pred, ps, ps.M, ps.native, ps.on_device
-        self.y_scale, self.y_shift = (float(pipe.y_std), float(pipe.y_mean)) if pipe.standardize_target else (1.0, 0.0)
-        self.y32 = y64.astype(np.float32)  # the kernel's target format; the oracle scores against the same values
-        if ps.rows is not None:
-            self.y32 = self.y32[ps.rows]
-        self.y64 = self.y32.astype(np.float64)
-        if self.on_device:
+    def __init__(self, scorer, y64: np.ndarray):
+        self.scorer, self.device = scorer, scorer.on_device
+        if scorer.learned:
+            y32 = y64.astype(np.float32)
+            y32 = y32 if scorer.rows is None else y32[scorer.rows]
+            y64 = y32.astype(np.float64)
+        self.y64 = y64
+        if self.device:
             from .ops.native import err_sums_scratch
 
-            self.perm_device, self.perm_dtype = pred.device, torch.int32
-            self.scratch = err_sums_scratch(pred.device)
-            self.y_dev = torch.from_numpy(self.y32).to(pred.device)
+            self.scratch = err_sums_scratch(scorer.pred.device)
+            self.y_dev = torch.from_numpy(y32).to(scorer.pred.device)
 
-    def begin(self, passes):
-        if self.on_device:
-            self.out = torch.zeros((passes, 2), dtype=torch.float64, device=self.pred.device)
+    def begin(self, passes: int) -> None:
+        if self.device:
+            self.out = torch.zeros((passes, 2), dtype=torch.float64, device=self.scorer.pred.device)
         else:
-            super().begin(passes)
+            self.sums = np.zeros((passes, 2), np.float64)
 
-    def finish(self):
-        self.pred.eng.check_device_errors()
-        return self.out.cpu().numpy() if self.on_device else self.sums
-
-    def reduce(self, slot):
+    def reduce(self, slot: int) -> None:
         from .ops.native import err_sums
 
-        err_sums(self.ps.p, self.y_dev, self.y_scale, self.y_shift, self.out, slot, self.scratch)
+        s = self.scorer
+        err_sums(s.ps.p, self.y_dev, s.y_scale, s.y_shift, self.out, slot, self.scratch)
 
-    def score(self, slot, k, perm):
-        p = self.ps.score(k, perm)
-        if self.on_device:
+    def score(self, slot: int, edit=None) -> None:
+        s = self.scorer
+        p = s.predict(edit)
+        if self.device:
             self.reduce(slot)
         else:
-            self.sums[slot] = _err_sums_host(torch.as_tensor(p).cpu().numpy(), self.y64, self.y_scale, self.y_shift)
+            self.sums[slot] = _err_sums_host(torch.as_tensor(p).cpu().numpy(), self.y64, s.y_scale, s.y_shift)
+
+    def finish(self) -> np.ndarray:
+        self.scorer.check_device_errors()
+        return self.out.cpu().numpy() if self.device else self.sums
 
 
 # ---------------------------------------------------------------------- the job
 def _write_csv(path: str, rows: list) -> None:
-    """One row per column, most important first; always with a header. Atomic (tmp + rename)."""
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = path + ".tmp"
-    with open(tmp, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(CSV_COLUMNS)
-        for d in rows:
-            w.writerow([d[c] if isinstance(d[c], str) else repr(float(d[c])) for c in CSV_COLUMNS])
-    os.replace(tmp, path)
+    """One row per column, most important first; always with a header."""
+    write_csv(path, CSV_COLUMNS, ([d[c] if isinstance(d[c], str) else repr(float(d[c])) for c in CSV_COLUMNS] for d in rows))
 
 
 def run_importance(model: str, argv, log=print) -> dict:
@@ -270,12 +179,11 @@ def run_importance(model: str, argv, log=print) -> dict:
 
     ns, cfg, schema, out_path, load_predictor, load_data = scoring_job(
         "importance", "importance", "importance", "dataPath (the data: held-out rows)", model, argv, add_arguments)
-    if int(os.environ.get("RANK", "0")) != 0:  # one process on one device: rank 0 alone works and writes
-        return {"model": model, "out": out_path, "skipped": True}
+    if skipped := other_rank(model, out_path):
+        return skipped
     job = PermutationImportance(load_predictor(), repeats=ns.repeats, seed=cfg.seed)
     table = load_data()
-    columns = [c.strip() for c in ns.columns.split(",") if c.strip()] if ns.columns is not None else None
-    result = job.run(table, columns=columns, target=cfg.target)
+    result = job.run(table, columns=comma_list(ns.columns), target=cfg.target)
     result["out"] = out_path
     _write_csv(out_path, result["importance"])
     log("Rows scored: %d" % result["scored"])

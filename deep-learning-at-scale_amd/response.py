@@ -34,19 +34,17 @@ mean of the same group. The overall cell adds the groups' sums on the host, in g
 """
 from __future__ import annotations
 
-import csv
 import math
-import os
 import sys
 
 import numpy as np
 import torch
 
-from .models.gilbert import GilbertModel
 from .predict import Predictor, scoring_job
-from .scoring import Constant, LstmPass, MlpPass
+from .scoring import ConstantColumn
+from .whatif import comma_list, input_columns, other_rank, scorer_for, select_columns, table_rows, write_csv
 
-GILBERT_INPUTS = ("whp", "choke", "glr")
+NO_COLUMN = "no column to sweep: name the columns (--columns a[,b..])"
 CSV_COLUMNS = ("column", "kind", "value", "group", "rows", "mean_prediction", "std_prediction", "delta")
 
 
@@ -80,29 +78,7 @@ class ResponseCurves:
     # ------------------------------------------------------------------ columns and grids
     def input_columns(self) -> list:
         """[(name, kind)] in the assembly kernel's source order (categorical, then continuous)."""
-        if self.pred.name == "gilbert":
-            return [(c, "continuous") for c in GILBERT_INPUTS]
-        pipe = self.pred.pipe
-        return [(ix.column, "categorical") for ix in pipe.indexers] + [(c, "continuous") for c in pipe.continuous]
-
-    def _select(self, columns) -> list:
-        have = self.input_columns()
-        names = [c for c, _ in have]
-        if columns is None or not list(columns):
-            raise ValueError("no column to sweep: name the columns (--columns a[,b..])")
-        target = self.pred.pipe.target if self.pred.pipe is not None else None
-        picked = []
-        for c in columns:
-            if c == target:
-                raise ValueError(f"column {c!r} is the target column: a response curve sets an INPUT column")
-            if c not in names:
-                what = ("gilbert reads only " + ", ".join(GILBERT_INPUTS)) if self.pred.name == "gilbert" else \
-                    f"the model's input columns are {names}"
-                raise ValueError(f"unknown column {c!r}: {what}")
-            if names.index(c) in picked:
-                raise ValueError(f"column {c!r} listed twice")
-            picked.append(names.index(c))
-        return picked
+        return input_columns(self.pred)
 
     def _grid(self, table: dict, name: str, kind: str, values):
         """(values as written, host values, codes or None) of one column's grid."""
@@ -135,14 +111,10 @@ class ResponseCurves:
     # ------------------------------------------------------------------ the run
     def run(self, table: dict, columns, grids=None, by: str | None = None) -> dict:
         pred = self.pred
-        picked = self._select(columns)
+        picked = select_columns(pred, columns, NO_COLUMN, default_all=False,
+                                target="a response curve sets an INPUT column")
         have = self.input_columns()
-        n = len(next(iter(table.values()))) if table else 0
-        if n < 1:
-            raise ValueError("no rows to score")
-        for c, _ in have:
-            if c not in table:
-                raise ValueError(f"the data lacks the input column {c!r}")
+        n = table_rows(pred, table)
         grids = dict(grids or {})
         for c in grids:
             if c not in [have[k][0] for k in picked]:
@@ -160,23 +132,17 @@ class ResponseCurves:
         if G > GROUP_SUMS_MAX_GROUPS:
             raise ValueError(f"--by {by!r} makes {G} groups; at most {GROUP_SUMS_MAX_GROUPS} are supported")
         plan = [(k, *self._grid(table, have[k][0], have[k][1], grids.get(have[k][0]))) for k in picked]
-        if pred.name == "gilbert":
-            scorer = _GilbertScorer(pred, table, row_ids, G)
-        else:
-            scorer = LearnedScorer(pred, table, row_ids, G, self.piece_rows)
-        if scorer.M < 1:
-            raise ValueError(f"no row can be scored: every series is shorter than the window of {pred.seq_len} rows")
-        passes = 1 + sum(len(shown) for _, shown, _, _ in plan)
-        scorer.begin(passes)
+        scorer = scorer_for(pred, table, "response", self.piece_rows)
+        grp = GroupSums(scorer, row_ids, G)
+        grp.begin(1 + sum(len(shown) for _, shown, _, _ in plan))
         with torch.no_grad():
-            scorer.score(0, -1, None)
+            grp.score(0)
             slot = 1
             for k, shown, host, codes in plan:
-                consts = scorer.constants(k, host, codes)  # one upload of the whole grid
-                for c in consts:
-                    scorer.score(slot, k, c)
+                for c in grp.constants(k, host, codes):  # one upload of the whole grid
+                    grp.score(slot, c)
                     slot += 1
-        sums = scorer.finish()  # float64 [passes][G][3]: the one read of the device
+        sums = grp.finish()  # float64 [passes][G][3]: the one read of the device
         curves = []
 
         def cells(slot, column, kind, value):
@@ -206,95 +172,58 @@ class ResponseCurves:
                 "baseline_mean": curves[0]["mean_prediction"]}
 
 
-# ---------------------------------------------------------------------- scorers
-class _Scorer:
-    """One table, scored again and again with one column set to a constant. ``score(slot, k,
-    const)`` leaves the pass's grouped sums in ``slot``; ``finish()`` returns them all."""
+# ---------------------------------------------------------------------- the reduction
+class GroupSums:
+    """``score(slot, edit)`` scores the edited table (whatif.py) and leaves the pass's grouped sums
+    in ``slot``; ``finish()`` returns them all. The sums are formed on the device (csrc/score.hip)
+    when the NATIVE engine scored (the predictions are there, whichever side assembled), else in
+    numpy. A prediction belongs to its row (MLP) or to the last row of its window (LSTM)."""
 
-    native = False
-
-    def begin(self, passes: int) -> None:
-        self.sums = np.zeros((passes, self.G, 3), np.float64)
-
-    def finish(self) -> np.ndarray:
-        return self.sums
-
-    def constants(self, k, host, codes):
-        return [Constant(h) for h in host]
-
-
-class _GilbertScorer(_Scorer):
-    """The physical model in host float64: its curve is what a learned curve is compared with."""
-
-    def __init__(self, pred, table, row_ids, G):
-        self.model = GilbertModel(correlation=pred.extra.get("correlation", "gilbert"))
-        self.cols = {k: np.asarray(table[k], np.float64) for k in GILBERT_INPUTS}
-        self.ids, self.G, self.M = row_ids, G, len(row_ids)
-
-    def score(self, slot, k, const):
-        cols = self.cols
-        if k >= 0:
-            cols = dict(cols)
-            cols[GILBERT_INPUTS[k]] = np.full(self.M, const.host, np.float64)
-        self.sums[slot] = group_sums_host(np.asarray(self.model.predict(cols), np.float64), self.ids, self.G)
-
-
-class LearnedScorer(_Scorer):
-    """The MLP and the LSTM: one pass of scoring.py per ``score``, then the grouped sums — on the
-    device (csrc/score.hip) when the native engine scored, else in numpy. A prediction belongs to
-    its row (MLP) or to the last row of its window (LSTM)."""
-
-    def __init__(self, pred, table, row_ids, G, piece_rows: int = 0):
-        pipe = pred.pipe
-        if pred.name == "lstm":
-            ps = LstmPass(pred, table, "LSTM response scoring")
-        else:
-            ps = MlpPass(pred, table, "MLP response scoring", resident=True, piece_rows=piece_rows)
-        self.pred, self.ps, self.M, self.native, self.on_device = pred, ps, ps.M, ps.native, ps.on_device
-        self.G = G
-        self.ids = row_ids if ps.rows is None else row_ids[ps.rows]
-        self.y_scale, self.y_shift = (float(pipe.y_std), float(pipe.y_mean)) if pipe.standardize_target else (1.0, 0.0)
-        if self.native and self.M >= 1:
+    def __init__(self, scorer, row_ids: np.ndarray, G: int):
+        self.scorer, self.G, self.device = scorer, G, scorer.native
+        self.ids = row_ids if scorer.rows is None else row_ids[scorer.rows]
+        if self.device:
             from .ops.native import GroupPlan
 
-            self.plan = GroupPlan(self.ids, G, pred.device)
+            self.plan = GroupPlan(self.ids, G, scorer.pred.device)
 
-    def begin(self, passes):
-        if self.native:
-            self.out = torch.zeros((passes, self.G, 3), dtype=torch.float64, device=self.pred.device)
+    def begin(self, passes: int) -> None:
+        if self.device:
+            self.out = torch.zeros((passes, self.G, 3), dtype=torch.float64, device=self.scorer.pred.device)
         else:
-            super().begin(passes)
+            self.sums = np.zeros((passes, self.G, 3), np.float64)
 
-    def finish(self):
-        self.pred.eng.check_device_errors()
-        return self.out.cpu().numpy() if self.native else self.sums
+    def constants(self, k: int, host, codes) -> list:
+        """The edits of one column's grid; the device assembly reads element g of one upload."""
+        if not self.scorer.on_device:
+            return [ConstantColumn(k, h) for h in host]
+        grid = torch.from_numpy(codes if codes is not None else np.asarray(host, np.float32)).to(self.scorer.pred.device)
+        return [ConstantColumn(k, h, grid[g : g + 1]) for g, h in enumerate(host)]
 
-    def constants(self, k, host, codes):
-        if not self.on_device:
-            return [Constant(h) for h in host]
-        grid = torch.from_numpy(codes if codes is not None else np.asarray(host, np.float32)).to(self.pred.device)
-        return [Constant(h, grid[g : g + 1]) for g, h in enumerate(host)]  # pass g points at element g
-
-    def reduce(self, slot):
+    def reduce(self, slot: int) -> None:
         from .ops.native import group_sums
 
-        group_sums(self.ps.p, self.plan, self.y_scale, self.y_shift, self.out, slot)
+        s = self.scorer
+        group_sums(s.ps.p, self.plan, s.y_scale, s.y_shift, self.out, slot)
 
-    def score(self, slot, k, const):
-        p = self.ps.score(k, None, const)
-        if self.native:
+    def score(self, slot: int, edit=None) -> None:
+        s = self.scorer
+        p = s.predict(edit)
+        if self.device:
             self.reduce(slot)
         else:
-            v = np.asarray(p).astype(np.float64) * self.y_scale + self.y_shift
+            v = np.asarray(p).astype(np.float64) * s.y_scale + s.y_shift
             self.sums[slot] = group_sums_host(v, self.ids, self.G)
+
+    def finish(self) -> np.ndarray:
+        self.scorer.check_device_errors()
+        return self.out.cpu().numpy() if self.device else self.sums
 
 
 # ---------------------------------------------------------------------- the job
 def _write_csv(path: str, rows: list) -> None:
     """Baseline rows first, then column by column, value by value, overall then groups; always with
-    a header; a cell without rows is left empty. Atomic (tmp + rename)."""
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = path + ".tmp"
+    a header; a cell without rows is left empty."""
 
     def cell(v):
         if v is None:
@@ -303,12 +232,7 @@ def _write_csv(path: str, rows: list) -> None:
             return str(v)
         return repr(float(v))
 
-    with open(tmp, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(CSV_COLUMNS)
-        for d in rows:
-            w.writerow([cell(d[c]) for c in CSV_COLUMNS])
-    os.replace(tmp, path)
+    write_csv(path, CSV_COLUMNS, ([cell(d[c]) for c in CSV_COLUMNS] for d in rows))
 
 
 def run_response(model: str, argv, log=print) -> dict:
@@ -320,16 +244,16 @@ def run_response(model: str, argv, log=print) -> dict:
 
     ns, cfg, schema, out_path, load_predictor, load_data = scoring_job(
         "response", "response-curve", "response", "dataPath --columns a[,b..]", model, argv, add_arguments)
-    columns = [c.strip() for c in ns.columns.split(",") if c.strip()] if ns.columns is not None else []
+    columns = comma_list(ns.columns)
     if not columns:
-        raise ValueError("no column to sweep: name the columns (--columns a[,b..])")
+        raise ValueError(NO_COLUMN)
     if ns.grid is not None and len(columns) > 1:
         raise ValueError(f"--grid gives ONE column's values; {len(columns)} columns are named (run them one by one)")
-    if int(os.environ.get("RANK", "0")) != 0:  # one process on one device: rank 0 alone works and writes
-        return {"model": model, "out": out_path, "skipped": True}
+    if skipped := other_rank(model, out_path):
+        return skipped
     job = ResponseCurves(load_predictor(), points=ns.points)
     table = load_data()
-    grids = {columns[0]: [v.strip() for v in ns.grid.split(",") if v.strip()]} if ns.grid is not None else None
+    grids = {columns[0]: comma_list(ns.grid)} if ns.grid is not None else None
     result = job.run(table, columns, grids=grids, by=ns.by)
     result["out"] = out_path
     _write_csv(out_path, result["curves"])

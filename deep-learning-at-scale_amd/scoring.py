@@ -13,15 +13,17 @@ routes:
   they are uploaded, and the same device loop scores them;
 * the fp32 oracle (CPU, or fp32 on a GPU): host rows through the PyTorch engine.
 
-``score(k, perm)`` returns the network outputs as fp32 ``[M]``: a device tensor (the pass's own
-buffer) on the native routes, a numpy array from the oracle. Source column ``k`` is read through
-the permutation ``perm`` (importance.py) or, with ``const``, set to one constant in every row
-(response.py); without either the table is scored as it is. ``score(perm=perm, cols=set)`` reads
-every source column of a :class:`ColumnSet` through ``perm`` (explain.py).
+``score(edit)`` returns the network outputs as fp32 ``[M]``: a device tensor (the pass's own
+buffer) on the native routes, a numpy array from the oracle. ``edit`` says how the table is edited
+for this pass: :class:`PermutedColumn` (one source column read through a permutation,
+importance.py), :class:`ConstantColumn` (one source column set to one constant in every row,
+response.py) or :class:`PermutedSet` (every source column of a set read through one permutation,
+explain.py); without an edit the table is scored as it is. An edit knows two things: how to apply
+itself to a host table, and what it tells the device assembly about rows ``[a, b)``.
 """
 from __future__ import annotations
 
-import collections
+import typing
 
 import numpy as np
 import torch
@@ -37,20 +39,6 @@ def permuted(table: dict, col: str, perm) -> dict:
     return t
 
 
-# One source column set to a constant. ``host``: the label (str) of a categorical column or the
-# np.float32 raw value of a continuous one, what the host routes write into the table; ``dev``: the
-# same value as a one-element device tensor (the int32 label code / the float32 value: an element
-# of a grid that was uploaded once), what the device assembly reads.
-Constant = collections.namedtuple("Constant", ["host", "dev"], defaults=[None])
-
-
-# A SET of source columns read through one permutation. ``host``: the source-column indices (the
-# kernel's source order), what the host routes permute one by one; ``dev``: the set's bitmask, a row
-# of ``ops.native.column_masks`` on the device (a job uploads the masks of all its passes once and
-# a pass points at its row), what the device assembly reads.
-ColumnSet = collections.namedtuple("ColumnSet", ["host", "dev"], defaults=[None])
-
-
 def constant(table: dict, col: str, value) -> dict:
     """The table with column ``col`` set to ``value`` in every row: a label (str) gives an object
     column, anything else a float32 column (the pipeline casts continuous columns to float32)."""
@@ -58,6 +46,64 @@ def constant(table: dict, col: str, value) -> dict:
     t = dict(table)
     t[col] = np.full(n, value, object) if isinstance(value, str) else np.full(n, value, np.float32)
     return t
+
+
+def _host_perm(perm) -> np.ndarray:
+    return torch.as_tensor(perm).cpu().numpy()
+
+
+class PermutedColumn(typing.NamedTuple):
+    """Source column ``k`` (the kernel's source order) read through ``perm``: a vector over ALL rows,
+    int32 on the device for the device assembly."""
+
+    k: int
+    perm: typing.Any
+    what = "a permuted pass"
+
+    def apply(self, table: dict, names) -> dict:
+        return permuted(table, names[self.k], _host_perm(self.perm))
+
+    def assemble_args(self, a: int, b: int) -> dict:
+        return {"perm": self.perm[a:b], "perm_col": self.k}
+
+
+class ConstantColumn(typing.NamedTuple):
+    """Source column ``k`` set to a constant. ``host``: the label (str) of a categorical column or
+    the np.float32 raw value of a continuous one, what the host routes write into the table;
+    ``dev``: the same value as a one-element device tensor (the int32 label code / the float32
+    value: an element of a grid that was uploaded once), what the device assembly reads."""
+
+    k: int
+    host: typing.Any
+    dev: typing.Any = None
+    what = "a constant pass"
+
+    def apply(self, table: dict, names) -> dict:
+        return constant(table, names[self.k], self.host)
+
+    def assemble_args(self, a: int, b: int) -> dict:
+        return {"const_col": self.k, "const_value": self.dev}
+
+
+class PermutedSet(typing.NamedTuple):
+    """A SET of source columns read through one permutation ``perm`` (as :class:`PermutedColumn`).
+    ``host``: the source-column indices, what the host routes permute one by one; ``dev``: the set's
+    bitmask, a row of ``ops.native.column_masks`` on the device (a job uploads the masks of all its
+    passes once and a pass points at its row), what the device assembly reads."""
+
+    host: tuple
+    dev: typing.Any
+    perm: typing.Any
+    what = "a pass with a set of permuted columns"
+
+    def apply(self, table: dict, names) -> dict:
+        pn = _host_perm(self.perm)
+        for s in self.host:
+            table = permuted(table, names[s], pn)
+        return table
+
+    def assemble_args(self, a: int, b: int) -> dict:
+        return {"perm": self.perm[a:b], "col_set": self.dev}
 
 
 class _Pass:
@@ -86,63 +132,37 @@ class _Pass:
         pipe = self.pipe
         return ResidentColumns(codes, cont, *pipe.block_spec(), *pipe.scale(), self.pred.n_features, self.pred.device)
 
-    def _features(self, k: int, perm, const=None, cols=None) -> np.ndarray:
-        """The host pipeline's rows, source column ``k`` read through ``perm`` or set to ``const``,
-        or every source column of ``cols`` (a :class:`ColumnSet`) read through ``perm``."""
-        if cols is not None:
-            if k >= 0 or const is not None:
-                raise ValueError("a set of permuted columns is not combined with one permuted or constant column")
-            tab, pn = self.table, torch.as_tensor(perm).cpu().numpy()
-            for s in cols.host:
-                tab = permuted(tab, self.names[s], pn)
-            return self.pipe.features(tab)
-        if k >= 0 and const is not None:
-            return self.pipe.features(constant(self.table, self.names[k], const.host))
-        tab = self.table if k < 0 else permuted(self.table, self.names[k], torch.as_tensor(perm).cpu().numpy())
-        return self.pipe.features(tab)
+    def _features(self, edit=None) -> np.ndarray:
+        """The host pipeline's rows of the table, edited by ``edit``."""
+        return self.pipe.features(self.table if edit is None else edit.apply(self.table, self.names))
 
     def _input_format(self, X: torch.Tensor) -> torch.Tensor:
         return X
 
-    def assemble(self, a: int, b: int, k: int = -1, perm=None, host=None, const=None, cols=None) -> torch.Tensor:
+    def assemble(self, a: int, b: int, edit=None, host=None) -> torch.Tensor:
         """Rows [a, b) of the table as engine input, in the pass's piece buffer. Device assembly:
-        source column ``k`` (or -1) is read through ``perm`` (int32 device vector over ALL rows;
-        resident columns only) or set to ``const.dev`` (a :class:`Constant`; resident columns
-        only); or every source column of ``cols.dev`` (a :class:`ColumnSet`; resident columns
-        only) is read through ``perm``. ``host``: the host-built rows of the whole table instead
-        (host assembly with the native engine)."""
+        the table as it is or, from resident columns only, edited by ``edit``. ``host``: the
+        host-built rows of the whole table instead (host assembly with the native engine)."""
         X = self.X[: b - a]
         if host is not None:
             X.copy_(self._input_format(torch.from_numpy(host[a:b])))
-        elif cols is not None:
+        elif edit is not None:
             if self.res is None:
-                raise ValueError("a pass with a set of permuted columns reads resident columns (resident=True)")
-            if k >= 0 or const is not None:
-                raise ValueError("a set of permuted columns is not combined with one permuted or constant column")
-            if perm is None:
-                raise ValueError("a set of permuted columns needs perm")
-            self.res.assemble(self.dtype, rows=(a, b), perm=perm[a:b], col_set=cols.dev, out=X)
-        elif k >= 0 and const is not None:
-            if self.res is None:
-                raise ValueError("a constant pass reads resident columns (resident=True)")
-            self.res.assemble(self.dtype, rows=(a, b), const_col=k, const_value=const.dev, out=X)
+                raise ValueError(f"{edit.what} reads resident columns (resident=True)")
+            self.res.assemble(self.dtype, rows=(a, b), out=X, **edit.assemble_args(a, b))
         elif self.res is not None:
-            self.res.assemble(self.dtype, rows=(a, b), perm=None if k < 0 else perm[a:b], perm_col=k, out=X)
+            self.res.assemble(self.dtype, rows=(a, b), out=X)
         else:  # this piece's raw columns alone go up
-            if k >= 0:
-                raise ValueError("a permuted pass reads resident columns (resident=True)")
             self._resident(self.codes[:, a:b], self.cont[:, a:b]).assemble(self.dtype, out=X)
         return X
 
-    def score(self, k: int = -1, perm=None, const=None, cols=None):
-        """Network outputs fp32 [M], source column ``k`` (or -1: none) read through ``perm`` or,
-        with ``const`` (a :class:`Constant`), set to that value in every row; with ``cols`` (a
-        :class:`ColumnSet`) every source column of the set is read through ``perm``."""
+    def score(self, edit=None):
+        """Network outputs fp32 [M] of the table, edited by ``edit`` (None: as it is)."""
         if not self.native:
-            return self._score_host(self._features(k, perm, const, cols))
-        host = None if self.on_device else self._features(k, perm, const, cols)
+            return self._score_host(self._features(edit))
+        host = None if self.on_device else self._features(edit)
         for a, b in self.pieces:
-            self.forward(self.assemble(a, b, k, perm, host, const, cols), a)
+            self.forward(self.assemble(a, b, edit, host), a)
         return self.p
 
 

@@ -27,7 +27,6 @@ import json
 import os
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
@@ -39,50 +38,20 @@ if ROOT not in sys.path:
 from wellflow.data.features import FeaturePipeline, take  # noqa: E402
 from wellflow.data.io import load_table  # noqa: E402
 from wellflow.data.schema import parse_schema  # noqa: E402
-from wellflow.explain import LearnedScorer  # noqa: E402
-from wellflow.models import registry  # noqa: E402
+from wellflow.explain import Attribution  # noqa: E402
 from wellflow.ops.native import attr_step  # noqa: E402
-from wellflow.predict import Predictor  # noqa: E402
-from wellflow.utils.checkpoint import save_mdl  # noqa: E402
+from wellflow.scoring import PermutedSet  # noqa: E402
+from wellflow.whatif import LearnedScorer  # noqa: E402
+
+from throughput_common import _clock, _events, _median, _predictor  # noqa: E402
 
 NAMES = "well,field,t,whp,choke,glr,temp,water_cut,dsp,flow"
 TYPES = "string,string,int,float,float,float,float,float,float,float"
 
 
-def _clock(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0, out
-
-
-def _median(v):
-    return float(np.median(np.asarray(v, np.float64)))
-
-
-def _events(fn, launches=10):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches * 1e-3
-
-
-def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
-    p = os.path.join(tmp, "models", f"{name}.mdl")
-    extra = {"features": pipe.state()}
-    if job:
-        extra["job"] = job
-    save_mdl(p, name, registry.keras_layers(name, ref), extra)
-    return Predictor.load(p, schema, device="cuda", precision="bf16", batch=batch)
-
-
-def _measure(pred, table, scorer, repeats, host_passes, rounds, cyclic):
+def _measure(pred, table, att, repeats, host_passes, rounds, cyclic):
     """Interleaved device / host windows over all input columns."""
+    scorer = att.scorer
     ps = scorer.ps  # the pass (wellflow/scoring.py): its own assembly and forward steps are timed below
     n = len(table["flow"])
     dev = pred.device
@@ -92,9 +61,9 @@ def _measure(pred, table, scorer, repeats, host_passes, rounds, cyclic):
     gen.manual_seed(0)
     rng = np.random.default_rng(0)
     order = rng.permutation(K)
-    sets = scorer.column_sets([[int(k) for k in order[j:]] for j in range(K)], K)  # the passes of one repeat
+    sets = att.column_sets([[int(k) for k in order[j:]] for j in range(K)], K)  # the passes of one repeat
     ar = torch.arange(n, device=dev, dtype=torch.int32)
-    scorer.begin(K)
+    att.begin(K)
 
     def draw():
         if cyclic:  # the LSTM's default row map
@@ -105,10 +74,10 @@ def _measure(pred, table, scorer, repeats, host_passes, rounds, cyclic):
         with torch.no_grad():
             for _ in range(repeats):
                 perm = draw()
-                scorer.step(sets[0], perm, K, True)
+                att.step(sets[0], perm, K, True)
                 for j in range(K - 1):
-                    scorer.step(sets[j + 1], perm, int(order[j]), False)
-                scorer.last(int(order[K - 1]))
+                    att.step(sets[j + 1], perm, int(order[j]), False)
+                att.last(int(order[K - 1]))
 
     ys, sh = scorer.y_scale, scorer.y_shift
     rows = np.arange(n) if ps.rows is None else ps.rows
@@ -129,21 +98,21 @@ def _measure(pred, table, scorer, repeats, host_passes, rounds, cyclic):
         return acc
 
     with torch.no_grad():
-        scorer.full()
+        att.full()
     device_window()  # warm-up of both paths
     host_window()
     td, th = [], []
     for _ in range(rounds):
         td.append(_clock(device_window)[0] / (repeats * K))
         th.append(_clock(host_window)[0] / host_passes)
-    t_read, (acc, sq, _) = _clock(scorer.finish)  # the one read of the tables
+    t_read, (acc, sq, _) = _clock(att.finish)  # the one read of the tables
     # the terms of one device pass, each alone
     a, b = ps.pieces[0]  # one piece at these sizes
     M = scorer.M
     perm_r = torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)
     perm_c = (ar + n // 3) % n
     sizes = {"1": sets[K - 1], "half": sets[K - K // 2], "all": sets[0]}
-    assert [len(s.host) for s in sizes.values()] == [1, K // 2, K]
+    assert [len(host) for host, _ in sizes.values()] == [1, K // 2, K]
     copy_src = torch.empty(22 * M, dtype=torch.uint8, device=dev)  # attr_step moves 44 B per cell: 24 read, 20 written
     copy_dst = torch.empty_like(copy_src)
     terms = {"randperm": [], "assemble_plain": [], "forward": [], "attr_step": [], "copy_same_bytes": []}
@@ -154,10 +123,11 @@ def _measure(pred, table, scorer, repeats, host_passes, rounds, cyclic):
             terms["randperm"].append(_events(lambda: torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)))
             terms["assemble_plain"].append(_events(lambda: ps.assemble(a, b)))
             for s, cs in sizes.items():
-                terms[f"assemble_set_{s}_random"].append(_events(lambda: ps.assemble(a, b, perm=perm_r, cols=cs)))
-                terms[f"assemble_set_{s}_cyclic"].append(_events(lambda: ps.assemble(a, b, perm=perm_c, cols=cs)))
+                er, ec = PermutedSet(*cs, perm_r), PermutedSet(*cs, perm_c)
+                terms[f"assemble_set_{s}_random"].append(_events(lambda: ps.assemble(a, b, er)))
+                terms[f"assemble_set_{s}_cyclic"].append(_events(lambda: ps.assemble(a, b, ec)))
             terms["forward"].append(_events(lambda: ps.forward(ps.X[: b - a], a)))
-            terms["attr_step"].append(_events(lambda: attr_step(ps.p, scorer.p_prev, ys, sh, scorer.acc, scorer.sq, 0)))
+            terms["attr_step"].append(_events(lambda: attr_step(ps.p, att.p_prev, ys, sh, att.acc, att.sq, 0)))
             terms["copy_same_bytes"].append(_events(lambda: copy_dst.copy_(copy_src)))
     us = {k: _median(v) * 1e6 for k, v in terms.items()}
     res = ps.res
@@ -186,8 +156,9 @@ def bench_mlp(rows, repeats, host_passes, rounds, tmp):
     pipe = FeaturePipeline(schema, "flow", standardize_target=True).fit(take(table, np.arange(0, n, 32)))
     torch.manual_seed(0)
     pred = _predictor(tmp, "mlp", MLPRegressor(pipe.n_features, (256, 256)), pipe, schema)
-    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table))
-    rec = _measure(pred, table, scorer, repeats, host_passes, rounds, cyclic=False)
+    t_setup, att = _clock(lambda: Attribution(LearnedScorer(pred, table, "attribution")))
+    scorer = att.scorer
+    rec = _measure(pred, table, att, repeats, host_passes, rounds, cyclic=False)
     rec.update(rows=n, features=pipe.n_features, engine_batch=pred.eng_batch, setup_s=t_setup, pieces=len(scorer.ps.pieces))
     return rec
 
@@ -205,8 +176,9 @@ def bench_lstm(repeats, host_passes, rounds, tmp):
     torch.manual_seed(0)
     pred = _predictor(tmp, "lstm", LSTMRegressor(pipe.n_features, H), pipe, schema,
                       job={"seq_len": T, "group_col": "well", "hidden": H, "mlp_hidden": [256, 256]}, batch=B)
-    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table))
-    rec = _measure(pred, table, scorer, repeats, host_passes, rounds, cyclic=True)
+    t_setup, att = _clock(lambda: Attribution(LearnedScorer(pred, table, "attribution")))
+    scorer = att.scorer
+    rec = _measure(pred, table, att, repeats, host_passes, rounds, cyclic=True)
     pred.eng.check_device_errors()
     rec.update(rows=n, features=pipe.n_features, engine_batch=B, setup_s=t_setup)
     return rec

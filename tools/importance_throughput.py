@@ -26,7 +26,6 @@ import json
 import os
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
@@ -38,50 +37,19 @@ if ROOT not in sys.path:
 from wellflow.data.features import FeaturePipeline, take  # noqa: E402
 from wellflow.data.io import load_table  # noqa: E402
 from wellflow.data.schema import parse_schema  # noqa: E402
-from wellflow.importance import LearnedScorer  # noqa: E402
-from wellflow.models import registry  # noqa: E402
-from wellflow.predict import Predictor  # noqa: E402
-from wellflow.utils.checkpoint import save_mdl  # noqa: E402
+from wellflow.importance import ErrorSums  # noqa: E402
+from wellflow.scoring import PermutedColumn  # noqa: E402
+from wellflow.whatif import LearnedScorer  # noqa: E402
+
+from throughput_common import _clock, _events, _median, _predictor  # noqa: E402
 
 NAMES = "well,field,t,whp,choke,glr,temp,water_cut,dsp,flow"
 TYPES = "string,string,int,float,float,float,float,float,float,float"
 
 
-def _clock(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0, out
-
-
-def _median(v):
-    return float(np.median(np.asarray(v, np.float64)))
-
-
-def _events(fn, launches=10):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches * 1e-3
-
-
-def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
-    p = os.path.join(tmp, "models", f"{name}.mdl")
-    extra = {"features": pipe.state()}
-    if job:
-        extra["job"] = job
-    save_mdl(p, name, registry.keras_layers(name, ref), extra)
-    return Predictor.load(p, schema, device="cuda", precision="bf16", batch=batch)
-
-
-def _measure(pred, table, scorer, cols, passes, host_passes, rounds):
+def _measure(pred, table, err, cols, passes, host_passes, rounds):
     """Interleaved device / host windows over the columns ``cols`` (source indices), round robin."""
-    ps = scorer.ps  # the pass (wellflow/scoring.py): its own assembly and forward steps are timed below
+    ps = err.scorer.ps  # the pass (wellflow/scoring.py): its own assembly and forward steps are timed below
     n = len(table["flow"])
     dev = pred.device
     gen = torch.Generator(device=dev)
@@ -89,14 +57,14 @@ def _measure(pred, table, scorer, cols, passes, host_passes, rounds):
     rng = np.random.default_rng(0)
     y = np.asarray(table["flow"], np.float64)
     names = ps.names
-    scorer.begin(1 + passes)
+    err.begin(1 + passes)
 
     def device_window():
         with torch.no_grad():
             for i in range(passes):
                 perm = torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)
-                scorer.score(1 + i, cols[i % len(cols)], perm)
-        return scorer.finish()  # the one read of the sums
+                err.score(1 + i, PermutedColumn(cols[i % len(cols)], perm))
+        return err.finish()  # the one read of the sums
 
     def host_window():
         out = []
@@ -111,25 +79,25 @@ def _measure(pred, table, scorer, cols, passes, host_passes, rounds):
         return out
 
     with torch.no_grad():
-        scorer.score(0, -1, None)
+        err.score(0)
     device_window()  # warm-up of both paths
     host_window()
     td, th = [], []
     for _ in range(rounds):
         td.append(_clock(device_window)[0] / passes)
         th.append(_clock(host_window)[0] / host_passes)
-    sums = scorer.finish()
+    sums = err.finish()
     # the terms of one device pass, each alone
     perm = torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)
-    k = cols[0]
+    edit = PermutedColumn(cols[0], perm)
     a, b = ps.pieces[0]  # one piece at these sizes
     terms = {"randperm_us": [], "assemble_us": [], "forward_us": [], "reduce_us": []}
     with torch.no_grad():
         for _ in range(max(rounds, 3)):
             terms["randperm_us"].append(_events(lambda: torch.randperm(n, generator=gen, device=dev, dtype=torch.int32)))
-            terms["assemble_us"].append(_events(lambda: ps.assemble(a, b, k, perm)))
+            terms["assemble_us"].append(_events(lambda: ps.assemble(a, b, edit)))
             terms["forward_us"].append(_events(lambda: ps.forward(ps.X[: b - a], a)))
-            terms["reduce_us"].append(_events(lambda: scorer.reduce(0)))
+            terms["reduce_us"].append(_events(lambda: err.reduce(0)))
     rec = {"device": {"pass_s": _median(td), "passes_per_s": 1.0 / _median(td), "all_pass_s": td, "passes_per_window": passes},
            "host": {"pass_s": _median(th), "passes_per_s": 1.0 / _median(th), "all_pass_s": th,
                     "passes_per_window": host_passes},
@@ -150,8 +118,9 @@ def bench_mlp(rows, passes, host_passes, rounds, tmp):
     pipe = FeaturePipeline(schema, "flow", standardize_target=True).fit(take(table, np.arange(0, n, 32)))
     torch.manual_seed(0)
     pred = _predictor(tmp, "mlp", MLPRegressor(pipe.n_features, (256, 256)), pipe, schema)
-    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table, np.asarray(table["flow"], np.float64)))
-    rec = _measure(pred, table, scorer, list(range(len(scorer.ps.names))), passes, host_passes, rounds)
+    t_setup, err = _clock(lambda: ErrorSums(LearnedScorer(pred, table, "importance"), np.asarray(table["flow"], np.float64)))
+    scorer = err.scorer
+    rec = _measure(pred, table, err, list(range(len(scorer.ps.names))), passes, host_passes, rounds)
     rec.update(rows=n, features=pipe.n_features, engine_batch=pred.eng_batch, setup_s=t_setup,
                pieces=len(scorer.ps.pieces))
     return rec
@@ -170,8 +139,9 @@ def bench_lstm(passes, host_passes, rounds, tmp):
     torch.manual_seed(0)
     pred = _predictor(tmp, "lstm", LSTMRegressor(pipe.n_features, H), pipe, schema,
                       job={"seq_len": T, "group_col": "well", "hidden": H, "mlp_hidden": [256, 256]}, batch=B)
-    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table, np.asarray(table["flow"], np.float64)))
-    rec = _measure(pred, table, scorer, list(range(len(scorer.ps.names))), passes, host_passes, rounds)
+    t_setup, err = _clock(lambda: ErrorSums(LearnedScorer(pred, table, "importance"), np.asarray(table["flow"], np.float64)))
+    scorer = err.scorer
+    rec = _measure(pred, table, err, list(range(len(scorer.ps.names))), passes, host_passes, rounds)
     pred.eng.check_device_errors()
     rec.update(rows=n, windows=int(scorer.M), features=pipe.n_features, engine_batch=B, setup_s=t_setup)
     return rec

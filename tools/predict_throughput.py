@@ -24,7 +24,6 @@ import json
 import os
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
@@ -36,34 +35,12 @@ if ROOT not in sys.path:
 from wellflow.data.features import FeaturePipeline, take  # noqa: E402
 from wellflow.data.io import load_table  # noqa: E402
 from wellflow.data.schema import parse_schema  # noqa: E402
-from wellflow.models import registry  # noqa: E402
 from wellflow.ops import native  # noqa: E402
-from wellflow.predict import Predictor  # noqa: E402
-from wellflow.utils.checkpoint import save_mdl  # noqa: E402
+
+from throughput_common import _clock, _events, _median, _predictor  # noqa: E402
 
 NAMES = "well,field,t,whp,choke,glr,temp,water_cut,dsp,flow"
 TYPES = "string,string,int,float,float,float,float,float,float,float"
-
-
-def _clock(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0, out
-
-
-def _median(v):
-    return float(np.median(np.asarray(v, np.float64)))
-
-
-def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
-    p = os.path.join(tmp, "models", f"{name}.mdl")
-    extra = {"features": pipe.state()}
-    if job:
-        extra["job"] = job
-    save_mdl(p, name, registry.keras_layers(name, ref), extra)
-    return Predictor.load(p, schema, device="cuda", precision="bf16", batch=batch)
 
 
 @contextlib.contextmanager
@@ -173,14 +150,7 @@ def bench_kernel(pipe, table, rounds, launches=20):
             fn()
         for _ in range(rounds):
             for fn, acc in ((run_k, tk), (run_c, tc)):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record()
-                for _ in range(launches):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                acc.append(e0.elapsed_time(e1) / launches * 1e-3)
+                acc.append(_events(fn, launches))
         out[label] = {"rows": n, "ld": ld, "bytes": nbytes, "kernel_us": _median(tk) * 1e6,
                       "kernel_GBps": nbytes / _median(tk) / 1e9, "copy_us": _median(tc) * 1e6,
                       "copy_GBps": nbytes / _median(tc) / 1e9}

@@ -39,63 +39,32 @@ if ROOT not in sys.path:
 from wellflow.data.features import FeaturePipeline, take  # noqa: E402
 from wellflow.data.io import load_table  # noqa: E402
 from wellflow.data.schema import parse_schema  # noqa: E402
-from wellflow.models import registry  # noqa: E402
-from wellflow.predict import Predictor  # noqa: E402
-from wellflow.response import LearnedScorer, group_sums_host  # noqa: E402
+from wellflow.response import GroupSums, group_sums_host  # noqa: E402
 from wellflow.scoring import constant  # noqa: E402
-from wellflow.utils.checkpoint import save_mdl  # noqa: E402
+from wellflow.whatif import LearnedScorer  # noqa: E402
+
+from throughput_common import _clock, _events, _median, _predictor  # noqa: E402
 
 NAMES = "well,field,t,whp,choke,glr,temp,water_cut,dsp,flow"
 TYPES = "string,string,int,float,float,float,float,float,float,float"
 
 
-def _clock(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0, out
-
-
-def _median(v):
-    return float(np.median(np.asarray(v, np.float64)))
-
-
-def _events(fn, launches=10):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / launches * 1e-3
-
-
-def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
-    p = os.path.join(tmp, "models", f"{name}.mdl")
-    extra = {"features": pipe.state()}
-    if job:
-        extra["job"] = job
-    save_mdl(p, name, registry.keras_layers(name, ref), extra)
-    return Predictor.load(p, schema, device="cuda", precision="bf16", batch=batch)
-
-
-def _measure(pred, table, scorer, ids, G, passes, host_passes, rounds):
+def _measure(pred, table, grp, ids, G, passes, host_passes, rounds):
     """Interleaved device / host windows: the continuous column 'choke' swept over ``passes`` values."""
+    scorer = grp.scorer
     ps = scorer.ps  # the pass (wellflow/scoring.py): its own assembly and forward steps are timed below
     pipe = pred.pipe
     k = ps.names.index("choke")
     lo, hi = float(np.min(table["choke"])), float(np.max(table["choke"]))
     grid = list(np.linspace(lo, hi, passes, dtype=np.float64).astype(np.float32))
-    consts = scorer.constants(k, grid, None)  # the one upload of the grid
-    scorer.begin(1 + passes)
+    consts = grp.constants(k, grid, None)  # the one upload of the grid
+    grp.begin(1 + passes)
 
     def device_window():
         with torch.no_grad():
             for i in range(passes):
-                scorer.score(1 + i, k, consts[i])
-        return scorer.finish()  # the one read of the sums
+                grp.score(1 + i, consts[i])
+        return grp.finish()  # the one read of the sums
 
     def host_window():
         out = []
@@ -106,7 +75,7 @@ def _measure(pred, table, scorer, ids, G, passes, host_passes, rounds):
         return out
 
     with torch.no_grad():
-        scorer.score(0, -1, None)
+        grp.score(0)
     dsums = device_window()  # warm-up of both paths
     hsums = host_window()
     # the two paths agree: predict_table rounds the raw-unit prediction to fp32, the device keeps fp64
@@ -115,13 +84,13 @@ def _measure(pred, table, scorer, ids, G, passes, host_passes, rounds):
     for _ in range(rounds):
         td.append(_clock(device_window)[0] / passes)
         th.append(_clock(host_window)[0] / host_passes)
-    sums = scorer.finish()
+    sums = grp.finish()
     # the host-side grouping alone: M predictions already on the host -> three bincounts
     v = np.asarray(scorer.ps.p.cpu().numpy(), np.float64) * scorer.y_scale + scorer.y_shift
     tg = []
     for _ in range(max(rounds, 3)):
         t0 = time.perf_counter()
-        group_sums_host(v, scorer.ids, G)
+        group_sums_host(v, grp.ids, G)
         tg.append(time.perf_counter() - t0)
     # the D2H copy of the predictions + sync that the host grouping needs first
     tc = [_clock(lambda: scorer.ps.p.cpu())[0] for _ in range(max(rounds, 3))]
@@ -129,10 +98,10 @@ def _measure(pred, table, scorer, ids, G, passes, host_passes, rounds):
     terms = {"assemble_const_us": [], "assemble_plain_us": [], "forward_us": [], "group_sums_us": []}
     with torch.no_grad():
         for _ in range(max(rounds, 3)):
-            terms["assemble_const_us"].append(_events(lambda: ps.assemble(a, b, k, None, None, consts[0])))
+            terms["assemble_const_us"].append(_events(lambda: ps.assemble(a, b, consts[0])))
             terms["assemble_plain_us"].append(_events(lambda: ps.assemble(a, b)))
             terms["forward_us"].append(_events(lambda: ps.forward(ps.X[: b - a], a)))
-            terms["group_sums_us"].append(_events(lambda: scorer.reduce(0)))
+            terms["group_sums_us"].append(_events(lambda: grp.reduce(0)))
     rec = {"device": {"pass_s": _median(td), "passes_per_s": 1.0 / _median(td), "all_pass_s": td, "passes_per_window": passes},
            "host": {"pass_s": _median(th), "passes_per_s": 1.0 / _median(th), "all_pass_s": th,
                     "passes_per_window": host_passes},
@@ -156,8 +125,9 @@ def bench_mlp(rows, passes, host_passes, rounds, tmp):
     pred = _predictor(tmp, "mlp", MLPRegressor(pipe.n_features, (256, 256)), pipe, schema)
     groups, ids = np.unique(np.asarray(table["well"]).astype(str), return_inverse=True)
     ids = ids.reshape(-1).astype(np.int64)
-    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table, ids, len(groups)))
-    rec = _measure(pred, table, scorer, ids, len(groups), passes, host_passes, rounds)
+    t_setup, grp = _clock(lambda: GroupSums(LearnedScorer(pred, table, "response"), ids, len(groups)))
+    scorer = grp.scorer
+    rec = _measure(pred, table, grp, ids, len(groups), passes, host_passes, rounds)
     rec.update(rows=n, features=pipe.n_features, engine_batch=pred.eng_batch, setup_s=t_setup, pieces=len(scorer.ps.pieces))
     return rec
 
@@ -177,8 +147,9 @@ def bench_lstm(passes, host_passes, rounds, tmp):
                       job={"seq_len": T, "group_col": "well", "hidden": H, "mlp_hidden": [256, 256]}, batch=B)
     groups, ids = np.unique(np.asarray(table["well"]).astype(str), return_inverse=True)
     ids = ids.reshape(-1).astype(np.int64)
-    t_setup, scorer = _clock(lambda: LearnedScorer(pred, table, ids, len(groups)))
-    rec = _measure(pred, table, scorer, ids, len(groups), passes, host_passes, rounds)
+    t_setup, grp = _clock(lambda: GroupSums(LearnedScorer(pred, table, "response"), ids, len(groups)))
+    scorer = grp.scorer
+    rec = _measure(pred, table, grp, ids, len(groups), passes, host_passes, rounds)
     pred.eng.check_device_errors()
     rec.update(rows=n, windows=int(scorer.M), features=pipe.n_features, engine_batch=B, setup_s=t_setup)
     return rec
