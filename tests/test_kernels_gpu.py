@@ -280,6 +280,33 @@ def test_weight_gradient_tiles_match_reference(tile, ksplit, N):
     assert err < 2e-3 * ref.abs().max().item(), (tile, err)
 
 
+@pytest.mark.parametrize("tile", [0, 1, 3, 4, 5, 7])
+@pytest.mark.parametrize("K,ksplit", [(2048, 1), (2048, 4), (2048 + 64, 3)])
+@pytest.mark.parametrize("N", [576, 192, 320])
+def test_weight_gradient_tiles_exact(tile, K, ksplit, N):
+    """The tiles of test_weight_gradient_tiles_match_reference with integer operands in
+    {-2 .. 2}: every product and every partial sum is an integer below 2^24, so fp32 adds them
+    exactly in any order (MFMA accumulation, split-K atomics) and the result must equal float64
+    bit for bit — one wrong k-step, row block or fragment shows as a whole number. K = 2112 with
+    ksplit = 3 gives three splits of 11 k-steps of 64 (22 of 32): an odd count per split. A short
+    last split cannot be made on the 256-row tiles at all: equal_ksplit (csrc/gemm.hip) steps
+    nsplit down until 64 * nsplit divides K, so their splits are always equal. Tile 0's generic
+    path rounds kchunk up to 64 instead (launch_cfg), which at this K gives the same 3 x 704."""
+    from wellflow.ops.native import gemm
+
+    g = torch.Generator().manual_seed(11)
+    M = 512
+    Amn = torch.randint(-2, 3, (K, M), generator=g).to(DEV).to(torch.bfloat16)      # A(m, k) = Amn[k, m]
+    Bmn = torch.randint(-2, 3, (K + 1, N), generator=g).to(DEV).to(torch.bfloat16)  # one spare k-row (see above)
+    out = torch.zeros(M, N, device=DEV)
+    gemm(Amn, Bmn, M, N, K, a_mn=True, b_mn=True, outF=out, atomic=True, ksplit=ksplit, tile=tile)
+    torch.cuda.synchronize()
+    ref = Amn.double().t() @ Bmn[:K].double()
+    assert ref.abs().max().item() > 100 and ref.abs().max().item() < 2 ** 24
+    bad = (out.double() != ref).nonzero()
+    assert bad.shape[0] == 0, (tile, bad.shape[0], bad[:8].tolist())
+
+
 @pytest.mark.parametrize("tile", [2, 6, 8, 9, 10, 11, 12])
 def test_retired_and_unknown_weight_gradient_tiles_are_refused(tile):
     """The retired experiment ids and ids that never existed fail on the host, before any launch,
