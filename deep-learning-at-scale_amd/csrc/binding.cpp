@@ -968,6 +968,9 @@ void transpose_cast_bf16(const at::Tensor& src, int64_t lds, int64_t rows, int64
 // With set_mask (int32 [ceil((C + Q) / 32)] on the table's device, the bit pattern of the mask's
 // 32-bit words: bit s & 31 of word s >> 5 is source column s; perm given, perm_col and const_col
 // -1) EVERY source column of the set is read through `perm`: the Shapley-attribution pass.
+// With perm_values (fp32 [Ntot] on the table's device; perm and a CONTINUOUS perm_col given, no
+// set, no constant) the permuted column is read from that vector instead of the table's column:
+// output row r takes perm_values[clamp(perm[r])]: the set-point pass (one value per row).
 constexpr int64_t kAssembleMaxF = 512;
 
 void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor> cont,
@@ -975,7 +978,7 @@ void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor
                        c10::optional<at::Tensor> mean, c10::optional<at::Tensor> stdv, int64_t row0, int64_t N,
                        int64_t F, const at::Tensor& out, int64_t perm_col, c10::optional<at::Tensor> perm,
                        int64_t const_col, c10::optional<at::Tensor> const_value,
-                       c10::optional<at::Tensor> set_mask) {
+                       c10::optional<at::Tensor> set_mask, c10::optional<at::Tensor> perm_values) {
   const bool has_c = codes.has_value() && codes->defined() && codes->numel() > 0;
   const bool has_q = cont.has_value() && cont->defined() && cont->numel() > 0;
   int64_t Ntot = -1;
@@ -1018,6 +1021,20 @@ void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor
   pm.ld_src = Ntot;
   const bool has_p = perm.has_value() && perm->defined();
   const bool has_s = set_mask.has_value() && set_mask->defined();
+  const bool has_v = perm_values.has_value() && perm_values->defined();
+  if (has_v) {
+    TORCH_CHECK(!has_s, "assemble_features: perm_values is not combined with a set of permuted columns");
+    TORCH_CHECK(const_col < 0 && !(const_value.has_value() && const_value->defined()),
+                "assemble_features: perm_values is not combined with a constant column");
+    TORCH_CHECK(has_p && perm_col >= 0, "assemble_features: perm_values goes together with perm and perm_col");
+    TORCH_CHECK(perm_col >= C && perm_col < C + Q, "assemble_features: perm_values needs a continuous perm_col (",
+                C, " .. ", C + Q - 1, "), got ", perm_col);
+    TORCH_CHECK(perm_values->is_cuda() && perm_values->device() == out.device() &&
+                    perm_values->scalar_type() == at::kFloat && perm_values->is_contiguous() && perm_values->dim() == 1,
+                "assemble_features: perm_values must be a contiguous float32 vector on the table's device");
+    TORCH_CHECK(perm_values->numel() == Ntot, "assemble_features: perm_values holds ", perm_values->numel(),
+                " values for the table's ", Ntot, " rows");
+  }
   if (has_s) {
     TORCH_CHECK(perm_col < 0, "assemble_features: a set of permuted columns or ONE perm_col, not both");
     TORCH_CHECK(const_col < 0 && !(const_value.has_value() && const_value->defined()),
@@ -1051,6 +1068,7 @@ void assemble_features(c10::optional<at::Tensor> codes, c10::optional<at::Tensor
     pm.perm = perm->data_ptr<int>();
     pm.base = perm_col < C ? static_cast<const void*>(cp + perm_col * Ntot)
                            : static_cast<const void*>(xp + (perm_col - C) * Ntot);
+    if (has_v) pm.base = perm_values->data_ptr<float>();  // per-row values of the column, one per table row
     pm.n = Ntot;
   }
   const bool has_k = const_value.has_value() && const_value->defined();
@@ -1128,6 +1146,65 @@ void attr_step(const at::Tensor& p_cur, const at::Tensor& p_prev, double y_scale
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p_cur.device());
   wf::launch_attr_step(p_cur.data_ptr<float>(), p_prev.data_ptr<float>(), M, y_scale, y_shift,
                        acc.data_ptr<double>() + row * M, sq.data_ptr<double>() + row * M, start, cur_stream());
+}
+
+// Per-row bracket search (score.hip): one pass of a set-point run. p / want fp32 [M]; the state xs
+// fp32 [4][M] (lo, hi, best_x, xq), fs fp64 [3][M] (f_lo, f_hi, best_r), status int32 [M], all
+// contiguous; mode 0 first scan, 1 scan (both read the pass's value from grid_x, a one-element fp32
+// device array), 2 refine (reads xq; grid_x None). p / want must not overlap the state.
+// Stream-ordered; nothing is read back here.
+void solve_step(const at::Tensor& p, const at::Tensor& want, double y_scale, double y_shift, int64_t mode,
+                c10::optional<at::Tensor> grid_x, const at::Tensor& xs, const at::Tensor& fs, const at::Tensor& status) {
+  for (const at::Tensor* t : {&p, &want}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 1,
+                "solve_step: p / want must be contiguous fp32 GPU vectors");
+  }
+  const int64_t M = p.numel();
+  TORCH_CHECK(M >= 1 && want.numel() == M, "solve_step: p holds ", M, " elements, want ", want.numel(),
+              " (need the same, >= 1)");
+  TORCH_CHECK(mode >= wf::kSolveFirst && mode <= wf::kSolveRefine, "solve_step: mode ", mode, " outside 0 .. 2");
+  TORCH_CHECK(xs.defined() && xs.is_cuda() && xs.scalar_type() == at::kFloat && xs.is_contiguous() && xs.dim() == 2 &&
+                  xs.size(0) == 4 && xs.size(1) == M,
+              "solve_step: xs must be a contiguous fp32 [4][", M, "] GPU tensor");
+  TORCH_CHECK(fs.defined() && fs.is_cuda() && fs.scalar_type() == at::kDouble && fs.is_contiguous() && fs.dim() == 2 &&
+                  fs.size(0) == 3 && fs.size(1) == M,
+              "solve_step: fs must be a contiguous fp64 [3][", M, "] GPU tensor");
+  TORCH_CHECK(status.defined() && status.is_cuda() && status.scalar_type() == at::kInt && status.is_contiguous() &&
+                  status.dim() == 1 && status.numel() == M,
+              "solve_step: status must be a contiguous int32 [", M, "] GPU vector");
+  for (const at::Tensor* t : {&want, &xs, &fs, &status}) {
+    TORCH_CHECK(t->device() == p.device(), "solve_step: tensors on different devices");
+  }
+  const float* gx = nullptr;
+  const bool has_g = grid_x.has_value() && grid_x->defined();
+  if (mode != wf::kSolveRefine) {
+    TORCH_CHECK(has_g && grid_x->is_cuda() && grid_x->device() == p.device() && grid_x->scalar_type() == at::kFloat &&
+                    grid_x->is_contiguous() && grid_x->numel() == 1,
+                "solve_step: grid_x must be one contiguous fp32 element on the predictions' device (scan modes)");
+    gx = grid_x->data_ptr<float>();
+  }
+  // every array of the state against p and want: a thread reads p[i] / want[i] while others store
+  struct Span { const char* a; int64_t n; };
+  const Span state[] = {{static_cast<const char*>(xs.data_ptr()), 16 * M},
+                        {static_cast<const char*>(fs.data_ptr()), 24 * M},
+                        {static_cast<const char*>(status.data_ptr()), 4 * M}};
+  for (const at::Tensor* t : {&p, &want}) {
+    const char* a0 = static_cast<const char*>(t->data_ptr());
+    for (const Span& sp : state) {
+      TORCH_CHECK(a0 + 4 * M <= sp.a || sp.a + sp.n <= a0, "solve_step: p / want overlap the state");
+    }
+  }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = i + 1; j < 3; ++j) {
+      TORCH_CHECK(state[i].a + state[i].n <= state[j].a || state[j].a + state[j].n <= state[i].a,
+                  "solve_step: the state arrays overlap each other");
+    }
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
+  const bool ok = wf::launch_solve_step(p.data_ptr<float>(), want.data_ptr<float>(), M, y_scale, y_shift, (int)mode, gx,
+                                        xs.data_ptr<float>(), fs.data_ptr<double>(), status.data_ptr<int>(),
+                                        cur_stream());
+  TORCH_CHECK(ok, "solve_step: the launcher refused the shape");
 }
 
 // Grouped prediction sums (score.hip): out[slot][g] = {n_g, sum v, sum v^2}, v = pred * y_scale +
@@ -1486,14 +1563,16 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(gather_rows);
   WF_DEF(transpose_cast_bf16);
   WF_DEF(im2col1d);
-  // const_col / const_value / set_mask are optional (and keywords): the twelve-argument call is the launch it was
+  // const_col / const_value / set_mask / perm_values are optional (and keywords): the twelve-argument call is the
+  // launch it was
   m.def("assemble_features", &Checked<&assemble_features>::call, py::arg("codes"), py::arg("cont"), py::arg("cat_off"),
         py::arg("cat_size"), py::arg("mean"), py::arg("std"), py::arg("row0"), py::arg("N"), py::arg("F"), py::arg("out"),
         py::arg("perm_col"), py::arg("perm"), py::arg("const_col") = -1, py::arg("const_value") = py::none(),
-        py::arg("set_mask") = py::none());
+        py::arg("set_mask") = py::none(), py::arg("perm_values") = py::none());
   WF_DEF(err_sums);
   WF_DEF(group_sums);
   WF_DEF(attr_step);
+  WF_DEF(solve_step);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
   m.def("cnn_fused_ok", &cnn_fused_ok);

@@ -369,4 +369,18 @@ bool launch_group_sums(const float* pred, const int* order, const int* piece_fir
                        const int* group_pieces, long M, int pieces, int G, double y_scale, double y_shift,
                        double* out, double* partial, hipStream_t s);
 
+// ---- per-row bracket search (score.hip) ----
+// One pass of a set-point run over M >= 1 predictions: r = (double)p * y_scale + y_shift -
+// (double)want (fp64, never contracted) moves the row's state xs fp32 [4][M] = {lo, hi, best_x, xq},
+// fs fp64 [3][M] = {f_lo, f_hi, best_r}, status int32 [M] (0 open, 1 bracketed) by the rule written
+// out in score.hip. mode: kSolveFirst / kSolveScan read the pass's value from the one-element device
+// array grid_x, kSolveRefine reads the row's own xq (grid_x unused, may be nullptr). One thread per
+// row, plain loads and stores: bitwise equal to a numpy replay. p / want must not overlap the state.
+// false = refused, nothing launched.
+constexpr int kSolveFirst = 0;
+constexpr int kSolveScan = 1;
+constexpr int kSolveRefine = 2;
+bool launch_solve_step(const float* p, const float* want, long M, double y_scale, double y_shift, int mode,
+                       const float* grid_x, float* xs, double* fs, int* status, hipStream_t s);
+
 }  // namespace wf

@@ -1,6 +1,7 @@
 // wellflow — scoring reductions on the device (gfx950): the error sums of a pass (err_sums, below),
-// the per-row attribution accumulation over two passes (attr_step) and the grouped prediction sums
-// of a pass (group_sums, last part of this file).
+// the per-row attribution accumulation over two passes (attr_step), the grouped prediction sums
+// of a pass (group_sums) and the per-row bracket search of a set-point run (solve_step, last part
+// of this file).
 //
 // A permutation-importance run (wellflow/importance.py) scores the table 1 + columns x repeats
 // times; every pass ends in this kernel instead of a D2H copy of the predictions and a host
@@ -303,6 +304,120 @@ bool launch_group_sums(const float* pred, const int* order, const int* piece_fir
                      piece_len, M, pieces, y_scale, y_shift, partial);
   hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)bb), dim3(64 * kGroupWaves), 0, s, partial, group_pieces,
                      pieces, G, out);
+  return true;
+}
+
+// ---- per-row bracket search (set points, wellflow/setpoint.py) ----
+//
+// A set-point run asks, per row, at which value of ONE input column the prediction meets a wanted
+// value: 1 + G + S passes, G over a grid of values (the same for every row), then S in which every
+// bracketed row is scored at the midpoint of its own bracket. Each pass ends in one grid-stride
+// elementwise launch that carries the row's state to the next pass. The residual is err_sums' d:
+//   r = (double)p * y_scale + y_shift - (double)want[i]        (fp64, never contracted)
+// State per prediction i: xs fp32 [4][M] = {lo, hi, best_x, xq}, fs fp64 [3][M] = {f_lo, f_hi,
+// best_r}, status int32 [M] (0 open, 1 bracketed). x: the value the column had in this pass.
+//   first scan (x = *grid_x): status = 0; lo = hi = best_x = x; f_lo = f_hi = best_r = r
+//   scan (x = *grid_x), open rows only, in this order:
+//     |r| < |best_r|, or best_r is NaN and r is not   ->  best_x = x, best_r = r   (strict: the first
+//                                                         of equal misses stays)
+//     (f_lo <= 0 && r >= 0) || (f_lo >= 0 && r <= 0)  ->  hi = x, f_hi = r, status = 1
+//     else                                            ->  lo = hi = x, f_lo = f_hi = r
+//   refine (x = xq[i]), bracketed rows only: r on f_lo's side of zero (f_lo < 0 ? r < 0 : f_lo > 0 ?
+//     r > 0 : false)  ->  lo = x, f_lo = r;  else hi = x, f_hi = r
+//   every pass ends with xq = status == 1 ? lo + (hi - lo) * 0.5f : best_x   (fp32)
+// A comparison with a NaN is false, so a NaN residual never brackets and reaches its own row only.
+// Cell i is read and written by ONE thread of the launch, with plain vector loads and stores: no
+// atomics, no LDS, no scratch, no state outside the arguments, so the state equals a numpy replay
+// bit for bit and two runs are bitwise equal. p / want must not overlap the state.
+namespace {
+
+__device__ __forceinline__ float solve_mid(float lo, float hi) {
+#pragma clang fp contract(off)
+  const float w = hi - lo;
+  const float h = w * 0.5f;
+  return lo + h;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void solve_step_kernel(const float* __restrict__ p, const float* __restrict__ want,
+                                                         long M, double y_scale, double y_shift, int mode,
+                                                         const float* __restrict__ grid_x, float* __restrict__ xs,
+                                                         double* __restrict__ fs, int* __restrict__ status) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  float* const lo_ = xs;
+  float* const hi_ = xs + M;
+  float* const bx_ = xs + 2 * M;
+  float* const xq_ = xs + 3 * M;
+  double* const flo_ = fs;
+  double* const fhi_ = fs + M;
+  double* const br_ = fs + 2 * M;
+  const float gx = mode == kSolveRefine ? 0.0f : grid_x[0];  // uniform: one scalar for every row
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < M; i += stride) {
+    const double r = score_err(p[i], want[i], y_scale, y_shift);
+    if (mode == kSolveFirst) {
+      lo_[i] = gx;
+      hi_[i] = gx;
+      bx_[i] = gx;
+      xq_[i] = gx;  // open: the best value so far
+      flo_[i] = r;
+      fhi_[i] = r;
+      br_[i] = r;
+      status[i] = 0;
+      continue;
+    }
+    const int st = status[i];
+    if (mode == kSolveScan) {
+      if (st != 0) continue;  // the first crossing in grid order stays (xq is the bracket's midpoint already)
+      float bx = bx_[i];
+      const double br = br_[i];
+      const double flo = flo_[i];
+      if (fabs(r) < fabs(br) || (br != br && r == r)) {
+        bx = gx;
+        bx_[i] = gx;
+        br_[i] = r;
+      }
+      if ((flo <= 0.0 && r >= 0.0) || (flo >= 0.0 && r <= 0.0)) {
+        hi_[i] = gx;
+        fhi_[i] = r;
+        status[i] = 1;
+        xq_[i] = solve_mid(lo_[i], gx);
+      } else {
+        lo_[i] = gx;
+        hi_[i] = gx;
+        flo_[i] = r;
+        fhi_[i] = r;
+        xq_[i] = bx;
+      }
+    } else {
+      if (st != 1) continue;  // open rows keep xq = best_x
+      const float x = xq_[i];
+      const double flo = flo_[i];
+      const bool same = flo < 0.0 ? r < 0.0 : (flo > 0.0 ? r > 0.0 : false);
+      float lo = lo_[i], hi = hi_[i];
+      if (same) {
+        lo = x;
+        lo_[i] = x;
+        flo_[i] = r;
+      } else {
+        hi = x;
+        hi_[i] = x;
+        fhi_[i] = r;
+      }
+      xq_[i] = solve_mid(lo, hi);
+    }
+  }
+}
+
+bool launch_solve_step(const float* p, const float* want, long M, double y_scale, double y_shift, int mode,
+                       const float* grid_x, float* xs, double* fs, int* status, hipStream_t s) {
+  if (M < 1 || mode < kSolveFirst || mode > kSolveRefine) return false;
+  if (mode != kSolveRefine && grid_x == nullptr) return false;
+  // capped grid, grid-stride over the rest: 8 workgroups per CU of a 256-CU device
+  long blocks = (M + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(solve_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, want, M, y_scale, y_shift, mode,
+                     grid_x, xs, fs, status);
   return true;
 }
 

@@ -97,7 +97,7 @@ class ResidentColumns:
         return (self.F + 7) // 8 * 8 if out_dtype == torch.bfloat16 else self.F
 
     def assemble(self, out_dtype, rows=None, perm=None, perm_col: int = -1, out=None, const_col: int = -1,
-                 const_value=None, col_set=None):
+                 const_value=None, col_set=None, perm_values=None):
         """Feature rows ``rows = (a, b)`` (default: all) of the resident table, as
         :func:`assemble_features` builds them. With ``perm`` (int32 device vector of ``b - a``
         indices into ALL N rows) source column ``perm_col`` — in the kernel's source order, the C
@@ -111,6 +111,11 @@ class ResidentColumns:
         With ``col_set`` (a row of :func:`column_masks`: int32 [ceil((C + Q) / 32)] on the table's
         device) EVERY source column of the set is read through ``perm`` (needed; ``perm_col`` stays
         -1): the set launch of the kernel. Not combined with ``perm_col`` or a constant.
+        With ``perm_values`` (a contiguous float32 vector over ALL N rows on the table's device;
+        together with ``perm`` and a CONTINUOUS ``perm_col``) the permuted column is read from
+        that vector instead of the table: output row r takes ``perm_values[perm[r]]`` through the
+        kernel's own standardisation, so with the identity ``perm[a:b]`` the column has one
+        value per row. Not combined with ``col_set`` or a constant.
         Everything is refused here, on the host, before a launch; nothing is uploaded."""
         import torch
 
@@ -118,6 +123,25 @@ class ResidentColumns:
         if not 0 <= a < b <= self.N:
             raise ValueError(f"assemble_features: rows [{a}, {b}) outside the table's {self.N} rows")
         perm_col = int(perm_col)
+        if perm_values is not None:
+            if col_set is not None:
+                raise ValueError("assemble_features: per-row values (perm_values) are not combined with a set of "
+                                 "permuted columns (col_set)")
+            if const_value is not None or int(const_col) >= 0:
+                raise ValueError("assemble_features: per-row values (perm_values) are not combined with a constant column")
+            if perm is None or perm_col < 0:
+                raise ValueError("assemble_features: perm_values goes together with perm and perm_col")
+            if not self.C <= perm_col < self.C + self.Q:
+                raise ValueError(f"assemble_features: perm_values needs a continuous perm_col "
+                                 f"([{self.C}, {self.C + self.Q})), got {perm_col}"
+                                 f"{' (a categorical column)' if 0 <= perm_col < self.C else ''}")
+            if not isinstance(perm_values, torch.Tensor) or perm_values.device != self.device:
+                raise ValueError(f"assemble_features: perm_values must be a tensor on {self.device}")
+            if perm_values.dtype != torch.float32:
+                raise TypeError(f"assemble_features: perm_values must be float32, got {perm_values.dtype}")
+            if perm_values.dim() != 1 or perm_values.numel() != self.N or not perm_values.is_contiguous():
+                raise ValueError(f"assemble_features: perm_values holds {tuple(perm_values.shape)} values for the "
+                                 f"table's {self.N} rows (a contiguous vector)")
         if col_set is not None:
             if perm_col >= 0:
                 raise ValueError("assemble_features: a set of permuted columns (col_set) or ONE perm_col, not both")
@@ -171,6 +195,10 @@ class ResidentColumns:
         if col_set is not None:
             lib().assemble_features(self.codes, self.cont, self.off, self.size, self.mean, self.std, a, b - a, self.F,
                                     out, -1, perm, set_mask=col_set)
+            return out
+        if perm_values is not None:
+            lib().assemble_features(self.codes, self.cont, self.off, self.size, self.mean, self.std, a, b - a, self.F,
+                                    out, perm_col, perm, perm_values=perm_values)
             return out
         lib().assemble_features(self.codes, self.cont, self.off, self.size, self.mean, self.std, a, b - a, self.F, out,
                                 perm_col if perm is not None else -1, perm, const_col if const_value is not None else -1,
@@ -245,6 +273,66 @@ def attr_step(p_cur, p_prev, y_scale: float, y_shift: float, acc, sq, row: int, 
     if not 0 <= int(row) < acc.shape[0]:
         raise ValueError(f"attr_step: row {row} outside [0, {acc.shape[0]})")
     lib().attr_step(p_cur, p_prev, float(y_scale), float(y_shift), acc, sq, int(row), bool(start))
+
+
+SOLVE_FIRST, SOLVE_SCAN, SOLVE_REFINE = 0, 1, 2  # csrc/kernels.h kSolveFirst / kSolveScan / kSolveRefine
+
+
+def _spans_overlap(t, u) -> bool:
+    a0, b0 = t.data_ptr(), u.data_ptr()
+    return not (a0 + t.numel() * t.element_size() <= b0 or b0 + u.numel() * u.element_size() <= a0)
+
+
+def solve_step(p, want, y_scale: float, y_shift: float, mode: int, grid_x, xs, fs, status):
+    """One pass of a set-point run (csrc/score.hip; the rule is wellflow/setpoint.py's
+    ``solve_step_host``): the residual ``r = p * y_scale + y_shift - want`` in uncontracted fp64
+    moves every row's state — ``xs`` float32 [4][M] (lo, hi, best_x, xq), ``fs`` float64 [3][M]
+    (f_lo, f_hi, best_r), ``status`` int32 [M] (0 open, 1 bracketed) — one thread per row, bit for
+    bit the numpy rule. ``mode``: ``SOLVE_FIRST`` / ``SOLVE_SCAN`` take the pass's value from
+    ``grid_x`` (a one-element float32 device tensor: an element of a grid uploaded once),
+    ``SOLVE_REFINE`` the row's own ``xq`` (``grid_x`` None). ``p`` / ``want``: float32 device
+    vectors [M] that do not overlap the state. Stream-ordered; nothing comes back to the host."""
+    import torch
+
+    for name, t in (("p", p), ("want", want)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"solve_step: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if p.dim() != 1 or p.shape != want.shape:
+        raise ValueError(f"solve_step: p {tuple(p.shape)} and want {tuple(want.shape)} must be equal vectors")
+    M = p.numel()
+    if M < 1:
+        raise ValueError("solve_step: no predictions (M < 1)")
+    if int(mode) not in (SOLVE_FIRST, SOLVE_SCAN, SOLVE_REFINE):
+        raise ValueError(f"solve_step: mode {mode} is not SOLVE_FIRST (0), SOLVE_SCAN (1) or SOLVE_REFINE (2)")
+    for name, t, dt, lead in (("xs", xs, torch.float32, 4), ("fs", fs, torch.float64, 3)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError(f"solve_step: {name} must be a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+        if tuple(t.shape) != (lead, M):
+            raise ValueError(f"solve_step: {name} must be [{lead}][{M}], got {tuple(t.shape)}")
+    if not isinstance(status, torch.Tensor) or status.dtype != torch.int32:
+        raise TypeError(f"solve_step: status must be an int32 tensor, got {getattr(status, 'dtype', type(status))}")
+    if tuple(status.shape) != (M,):
+        raise ValueError(f"solve_step: status must be [{M}], got {tuple(status.shape)}")
+    named = (("p", p), ("want", want), ("xs", xs), ("fs", fs), ("status", status))
+    if p.device.type != "cuda" or any(t.device != p.device for _, t in named):
+        raise ValueError("solve_step: the tensors must be on one GPU, got " + ", ".join(str(t.device) for _, t in named))
+    for name, t in named:
+        if not t.is_contiguous():
+            raise ValueError(f"solve_step: {name} must be contiguous")
+    if int(mode) == SOLVE_REFINE:
+        if grid_x is not None:
+            raise ValueError("solve_step: a refine pass reads every row's own xq; grid_x must be None")
+    else:
+        if not isinstance(grid_x, torch.Tensor) or grid_x.dtype != torch.float32:
+            raise TypeError(f"solve_step: grid_x must be a float32 tensor, got {getattr(grid_x, 'dtype', type(grid_x))}")
+        if grid_x.device != p.device or grid_x.numel() != 1 or not grid_x.is_contiguous():
+            raise ValueError(f"solve_step: grid_x must be one contiguous element on {p.device}, got "
+                             f"{tuple(grid_x.shape)} on {grid_x.device}")
+    for name, t in (("p", p), ("want", want)):
+        for sname, st in (("xs", xs), ("fs", fs), ("status", status)):
+            if _spans_overlap(t, st):
+                raise ValueError(f"solve_step: {name} overlaps the state ({sname})")
+    lib().solve_step(p, want, float(y_scale), float(y_shift), int(mode), grid_x, xs, fs, status)
 
 
 ERR_SUMS_SCRATCH = 2 * 256 + 1  # csrc/kernels.h kErrSumsScratch: a partial pair per workgroup + the ticket

@@ -17,8 +17,9 @@ routes:
 buffer) on the native routes, a numpy array from the oracle. ``edit`` says how the table is edited
 for this pass: :class:`PermutedColumn` (one source column read through a permutation,
 importance.py), :class:`ConstantColumn` (one source column set to one constant in every row,
-response.py) or :class:`PermutedSet` (every source column of a set read through one permutation,
-explain.py); without an edit the table is scored as it is. An edit knows two things: how to apply
+response.py), :class:`PermutedSet` (every source column of a set read through one permutation,
+explain.py) or :class:`RowValues` (one continuous source column set to its own value in every row,
+setpoint.py); without an edit the table is scored as it is. An edit knows two things: how to apply
 itself to a host table, and what it tells the device assembly about rows ``[a, b)``.
 """
 from __future__ import annotations
@@ -104,6 +105,28 @@ class PermutedSet(typing.NamedTuple):
 
     def assemble_args(self, a: int, b: int) -> dict:
         return {"perm": self.perm[a:b], "col_set": self.dev}
+
+
+class RowValues(typing.NamedTuple):
+    """Continuous source column ``k`` set to its own value in every row (setpoint.py). ``values``:
+    one float32 raw value per row of the table, a device vector for the device assembly (a numpy
+    array or a tensor for the host routes, which write it into the table as host float32);
+    ``ident``: the identity index vector over all rows, int32 on the device and uploaded once by
+    the job: rows ``[a, b)`` read ``values`` through ``ident[a:b]``, so a piece gathers from the
+    whole vector."""
+
+    k: int
+    values: typing.Any
+    ident: typing.Any = None
+    what = "a pass with per-row values"
+
+    def apply(self, table: dict, names) -> dict:
+        t = dict(table)
+        t[names[self.k]] = np.ascontiguousarray(torch.as_tensor(self.values).cpu().numpy(), dtype=np.float32)
+        return t
+
+    def assemble_args(self, a: int, b: int) -> dict:
+        return {"perm": self.ident[a:b], "perm_col": self.k, "perm_values": self.values}
 
 
 class _Pass:

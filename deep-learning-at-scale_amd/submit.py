@@ -16,6 +16,10 @@ per ``--by`` group: the model's response curves (wellflow/response.py).
 ``python -m wellflow.submit explain <model> columnNames columnTypes targetColumn storagePath dataPath``
 attributes every row's prediction to the input columns: per-row Shapley contributions in raw target
 units that, added to a base value, give the prediction (wellflow/explain.py).
+
+``python -m wellflow.submit setpoint <model> columnNames columnTypes targetColumn storagePath dataPath --column C --want V``
+searches, row by row, the value of one continuous input column at which the model predicts the wanted
+value (``--want-column COL``: one wanted value per row): the inverse of predict (wellflow/setpoint.py).
 """
 import sys
 
@@ -43,6 +47,10 @@ def main(argv=None) -> int:
         from .explain import main as explain_main
 
         return explain_main(argv[1:])
+    if argv[0] == "setpoint":  # per-row bracket search: the value of one input column that gives the wanted prediction
+        from .setpoint import main as setpoint_main
+
+        return setpoint_main(argv[1:])
     run_job(argv[0], argv[1:])
     return 0
 
