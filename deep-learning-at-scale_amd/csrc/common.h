@@ -78,8 +78,9 @@ __device__ __forceinline__ float tanhf_(float x) {
 }
 
 // Counter-based uniform in [0,1) (splitmix64 finaliser). Dropout masks are regenerated
-// from (seed, flat index) in the backward pass instead of being stored; the same
-// function is mirrored in wellflow/ops/reference.py for CPU tests.
+// from (seed, flat index) in the backward pass instead of being stored; the GEMM epilogue's
+// use of it (gemm.hip drop_seed) is mirrored bit for bit by wellflow/train/cnn_exact.py
+// gemm_dropout_mask for the exact-value tests.
 __device__ __forceinline__ float uniform_hash(unsigned long long seed, unsigned long long idx) {
   unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
