@@ -1,22 +1,7 @@
-"""Engine interface shared by every trainable model.
-
-An *engine* owns ONE flat fp32 parameter buffer and ONE flat fp32 gradient buffer (so the
-optimizer is a single launch and the data-parallel reduction a single collective) and
-exposes:
-
-    forward(x) -> pred                         (device tensor, no host sync)
-    forward_backward(x, y, grad_scale) -> loss_sum
-        computes d/dθ [grad_scale * Σ_i loss_i] into ``grads`` and returns Σ_i loss_i as a
-        device scalar; loss_i = (pred_i - y_i)^2 ("mse") or clip(|y_i - pred_i|, 0, c)
-        ("mae_clip", cnn.py:29-32).
-    sync_weights()                              refresh derived copies after an update
-    to_reference() / from_reference()           the model-family reference layout (.mdl)
-
-Native engines (NativeLSTM / NativeMLP / NativeCNN) run the hand-written HIP kernels;
-:class:`TorchEngine` wraps the fp32 PyTorch reference modules (the CPU oracle) with their
-parameters and gradients re-seated as views into flat buffers, so trainer, optimizer and
-DP all-reduce code paths are identical for both.
-"""
+"""The engine contract of every trainable model (:class:`Engine`). Native engines (NativeLSTM /
+NativeMLP / NativeCNN) run the hand-written HIP kernels; :class:`TorchEngine` wraps the fp32
+PyTorch reference modules (the CPU oracle) with their parameters and gradients re-seated as views
+into flat buffers, so trainer, optimizer and DP all-reduce code paths are identical for both."""
 from __future__ import annotations
 
 import torch
@@ -31,10 +16,95 @@ def per_element_loss(kind: str, pred: torch.Tensor, y: torch.Tensor, clip: float
     raise ValueError(f"unknown loss {kind!r}")
 
 
-class TorchEngine:
-    """fp32 PyTorch engine over a reference nn.Module (CPU oracle / GPU eager)."""
+class Engine:
+    """What train/ and the jobs ask of an engine. It owns ONE flat fp32 parameter buffer ``params``
+    and ONE flat fp32 gradient buffer ``grads`` on ``device`` (so the optimizer is a single launch
+    and the data-parallel reduction a single collective) and implements
 
-    native = False
+        forward(x) -> pred                         (device tensor, no host sync)
+        forward_backward(x, y, grad_scale, zero_grads=True, loss_into=None) -> loss_sum
+            computes d/dθ [grad_scale * Σ_i loss_i] into ``grads`` and returns Σ_i loss_i as a
+            device scalar (added to ``loss_into`` when given); loss_i = (pred_i - y_i)^2 ("mse")
+            or clip(|y_i - pred_i|, 0, c) ("mae_clip", cnn.py:29-32).
+
+    The rest has defaults: callers read it or call it, and a misspelt name is an AttributeError."""
+
+    native = False          # hand-written HIP kernels (fixed-shape batches, hipGraph replay)
+    row_indexed = False     # forward_backward(X, Y, ..., rows=) reads dataset rows in place
+    window_indexed = False  # ... reads resident SeriesWindows in place through window ids
+    input_dtype = None      # dtype resident datasets are kept in (None: as they come)
+    B = None                # batch capacity (None: any)
+    rng = None              # device step counter of the dropout stream (set on resume)
+    lay = None              # flat parameter layout; its repr is checked on resume
+    small = None            # SmallLaunchState of an engine with a K-steps-per-launch kernel
+    writeback_update = None  # "adam" / "sgd": the update this engine runs fused with its operand refresh
+
+    def to_input_format(self, X: torch.Tensor) -> torch.Tensor:
+        return X.to(self.input_dtype) if self.input_dtype is not None and X.dtype != self.input_dtype else X
+
+    def gather_rows(self, src: torch.Tensor, order: torch.Tensor, out: torch.Tensor) -> None:
+        torch.index_select(src, 0, order, out=out)  # the epoch's shuffle (Trainer._permuted)
+
+    def sync_weights(self) -> None:  # refresh the copies derived from ``params`` after an update
+        pass
+
+    def check_device_errors(self) -> None:
+        """Raise if a persistent launch since the last check left its work undone."""
+        if self.small is not None:
+            self.small.check()
+
+    def persistent_stats(self) -> dict:
+        return {}
+
+    def small_steps_reason(self, B: int, opt=None, X=None) -> str:
+        """None when K training steps of batch ``B`` can run as ONE launch (fused_steps), else why not."""
+        return "the engine has no K-steps-per-launch kernel"
+
+    def fused_steps(self, X, Y, B: int, K: int, opt, grad_scale: float, rows=None, loss_into=None) -> None:
+        raise RuntimeError(f"{type(self).__name__}.fused_steps: {self.small_steps_reason(B, opt, X)}")
+
+    def fused_update_kwargs(self, kind: str) -> dict:
+        """The make_optimizer kwargs with which the ``kind`` ("adam" / "sgd") update also refreshes
+        this engine's operand copies in its own launch; {}: sync_weights follows every update."""
+        return {"writeback": self} if kind == self.writeback_update else {}
+
+    def fused_update_ok(self, opt) -> bool:
+        """Whether the fused update that ``opt.writeback`` calls back on this engine covers ``opt``."""
+        return False
+
+    def update_refreshes_operands(self, opt) -> bool:
+        """Whether ``opt.step()`` leaves the operand copies current, so no sync_weights follows: it
+        is this engine's own fused update AND that covers ``opt`` (round-5 ADVICE: an LSTM with a
+        shadow-writing Adam ran the plain update and trained on stale copies)."""
+        return getattr(opt, "writeback", None) is self and self.fused_update_ok(opt)
+
+
+class SmallLaunchState:
+    """Host state of an engine's K-steps-per-launch kernel (csrc/mlp_small.hip, cnn_small.hip):
+    the exchange scratch and the 4 sync words, allocated by the first launch."""
+
+    def __init__(self, who: str):
+        self.who, self.scratch, self.sync = who, None, None
+
+    def buffers(self, scratch_floats, device):  # scratch_floats() sizes the scratch on first use
+        if self.scratch is None:
+            self.scratch = torch.zeros(scratch_floats(), device=device)
+            self.sync = torch.zeros(4, dtype=torch.int32, device=device)
+        return self.scratch, self.sync
+
+    def check(self) -> None:
+        """Raise if a launch's hand-off timed out (sticky word; the buffer is reset)."""
+        if self.sync is not None and int(self.sync[2].item()):
+            # all four words, as ever. That the tags of the next launch are stale after this reset
+            # (ADVICE item 1) is a behaviour fix for a change of its own
+            self.sync.zero_()
+            raise RuntimeError(f"{self.who}: a small-batch persistent launch timed out in a hand-off "
+                               "(results of that launch are invalid)")
+
+
+class TorchEngine(Engine):
+    """fp32 PyTorch engine over a reference nn.Module (CPU oracle / GPU eager). Its parameters
+    ARE views of the flat buffer, so there is nothing to sync."""
 
     def __init__(self, module: nn.Module, loss: str = "mse", clip: float = 6.0, device="cpu"):
         self.module = module.to(device)
@@ -52,21 +122,13 @@ class TorchEngine:
             p.grad = self.grads[o : o + k].view_as(p)
             o += k
 
-    def sync_weights(self) -> None:  # parameters ARE views of the flat buffer
-        pass
-
-    def check_device_errors(self) -> None:  # no persistent launches, so nothing to report
-        pass
-
-    def train(self, mode: bool = True):
-        self.module.train(mode)
-
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self.module.eval()
         with torch.no_grad():
             return self.module(x.to(self.device))
 
-    def forward_backward(self, x, y, grad_scale: float, zero_grads: bool = True, step: int = 0):
+    def forward_backward(self, x, y, grad_scale: float, zero_grads: bool = True, step: int = 0,
+                         loss_into: torch.Tensor | None = None):
         self.module.train()
         if zero_grads:
             self.grads.zero_()
@@ -74,11 +136,10 @@ class TorchEngine:
         li = per_element_loss(self.loss_kind, pred, y.to(self.device).view_as(pred), self.clip)
         total = li.sum()
         (total * grad_scale).backward()
+        if loss_into is not None:
+            loss_into += total.detach()
+            return loss_into
         return total.detach().view(1)
-
-
-def native_loss_kind(kind: str) -> int:
-    return {"mse": 0, "mae_clip": 1}[kind]
 
 
 # NativeMLP / NativeCNN.small_steps_reason, checked last: the K-steps-per-launch kernels update

@@ -31,7 +31,7 @@ import os
 import torch
 from torch import nn
 
-from .base import CLIP_STEPS_REASON, note_slow_path
+from .base import CLIP_STEPS_REASON, Engine, SmallLaunchState, note_slow_path
 
 
 def _r8(x: int) -> int:
@@ -200,13 +200,14 @@ def cnn_fast_path_reason(layout: "CnnLayout", dropout: float) -> str | None:
     return None
 
 
-class NativeCNN:
+class NativeCNN(Engine):
     """HIP/MFMA engine for the reference CNN (any batch up to ``batch``).
 
     ``fused`` (default where the shape allows, see module doc): three kernel launches per
     training step with the activation on chip; else the im2col + GEMM path."""
 
     native = True
+    writeback_update = "sgd"  # fused_sgd
 
     def __init__(self, layout: CnnLayout = CnnLayout(), batch: int = 1024, device="cuda",
                  dropout: float = 0.5, loss: str = "mae_clip", clip: float = 6.0, seed: int = 0,
@@ -226,6 +227,7 @@ class NativeCNN:
         # dropout step counter on the device: the mask differs every training step, eager or
         # replayed from a captured hipGraph (a host-side step would be baked into the graph)
         self.rng = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.small = SmallLaunchState("NativeCNN")  # K steps per launch (fused_steps)
         L = layout
         ok = self._C.cnn_fused_ok(L.fused_dims, float(dropout))
         why = cnn_fast_path_reason(L, float(dropout))
@@ -308,33 +310,26 @@ class NativeCNN:
         why = self.small_steps_reason(B, opt, X)
         if why is not None:
             raise RuntimeError(f"NativeCNN.fused_steps: {why}")
-        if getattr(self, "_small_scr", None) is None:
-            self._small_scr = torch.zeros(self._C.cnn_small_scratch_floats(), device=self.device)
-            self._small_sync = torch.zeros(4, dtype=torch.int32, device=self.device)
+        scr, sync = self.small.buffers(self._C.cnn_small_scratch_floats, self.device)
         kind = 0 if self.loss_kind == "mse" else 1
         ok = self._C.cnn_small_steps(X.reshape(-1), Y.reshape(-1).float(), rows, B, K, self.lay.fused_dims,
                                      float(self.p), kind, float(self.clip), float(grad_scale), self.seed32, self.rng,
                                      self.params, opt.vel, opt.step_dev, opt.lr, opt.decay, opt.momentum,
-                                     bool(opt.nesterov), 1.0, loss_into, self._small_scr, self._small_sync,
-                                     self.lay.filters, stamps)
+                                     bool(opt.nesterov), 1.0, loss_into, scr, sync, self.lay.filters, stamps)
         if not ok:
             raise RuntimeError("NativeCNN.fused_steps: the launcher refused the shape")
         opt.iterations += K
         self.sync_weights()  # the bf16 operand images of the regular kernels (evaluation)
 
-    def check_device_errors(self) -> None:
-        """Raise if a small-batch launch's hand-off timed out (sticky word; the buffer is reset)."""
-        sync = getattr(self, "_small_sync", None)
-        if sync is None:
-            return
-        if int(sync[2].item()):
-            sync.zero_()
-            raise RuntimeError("NativeCNN: a small-batch persistent launch timed out in a hand-off "
-                               "(results of that launch are invalid)")
-
     def fused_sgd_ok(self, opt) -> bool:
-        """Whether :meth:`fused_sgd` covers ``opt`` (train/step.py's sync_weights decision)."""
+        """Whether :meth:`fused_sgd` covers ``opt`` (the GEMM path has no fused update)."""
         return bool(self.fused)
+
+    fused_update_ok = fused_sgd_ok
+
+    def update_refreshes_operands(self, opt) -> bool:
+        # (the GEMM path reads the plain bf16 cast, which an Adam ``shadow`` writes)
+        return super().update_refreshes_operands(opt) if self.fused else getattr(opt, "shadow", None) is self.shadow
 
     def fused_sgd(self, opt, grad_scale: float) -> bool:
         """The optimizer's update and this engine's operand images in ONE launch (optim/flat.py

@@ -29,6 +29,8 @@ import sys
 import torch
 from torch import nn
 
+from .base import Engine
+
 
 def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
@@ -175,7 +177,7 @@ def init_lstm_flat(n_features: int, hidden: int, seed: int = 0) -> torch.Tensor:
     return flat
 
 
-class NativeLSTM:
+class NativeLSTM(Engine):
     """HIP/MFMA LSTM regression engine for a fixed (max) batch size.
 
     ``params``/``grads`` are flat fp32 device buffers in :class:`LstmLayout` order;
@@ -184,6 +186,7 @@ class NativeLSTM:
 
     native = True
     window_indexed = True  # forward_backward(windows, y, ..., rows=) reads the windows in place
+    writeback_update = "adam"  # fused_adam
 
     def __init__(self, n_features: int, hidden: int, seq_len: int, batch: int,
                  device="cuda", params: torch.Tensor | None = None,
@@ -270,10 +273,11 @@ class NativeLSTM:
 
     # ------------------------------------------------------------------ weights
     def fused_adam_ok(self, opt) -> bool:
-        """Whether :meth:`fused_adam` covers ``opt`` (train/step.py decides from the same
-        predicate whether the step still needs its own sync_weights launch)."""
+        """Whether :meth:`fused_adam` covers ``opt``."""
         # (the kernel transposes W_hh in 32 x 32 tiles)
         return opt.shadow is None and opt.shadow_t is None and self.H % 32 == 0 and self.lay.KX % 32 == 0
+
+    fused_update_ok = fused_adam_ok
 
     def fused_adam(self, opt, grad_scale: float) -> bool:
         """The optimizer's Adam update and this engine's bf16 compute copies (Wp, WhhT) in ONE

@@ -18,14 +18,12 @@ input width is padded to a multiple of 8 (zero columns).
 from __future__ import annotations
 
 import dataclasses
-import math
-
 import os
 
 import torch
 from torch import nn
 
-from .base import CLIP_STEPS_REASON, note_slow_path
+from .base import CLIP_STEPS_REASON, Engine, SmallLaunchState, note_slow_path
 
 
 # floats of the spread-reduction scratch (csrc/kernels.h kMlpRedFloats: 64 x 9216 copies,
@@ -139,11 +137,15 @@ def mlp_fast_path_reason(hidden, Fp: int, loss: str, B: int) -> str | None:
     return None
 
 
-class NativeMLP:
+class NativeMLP(Engine):
     """HIP/MFMA MLP regression engine for batches of up to ``batch`` rows."""
 
     native = True
     row_indexed = True  # forward_backward(..., rows=) reads dataset rows in place
+    # the MFMA input format: the Trainer keeps resident datasets in it (half the bytes of fp32,
+    # and the per-step gather IS the engine's input: no cast kernel): bf16 rows of Fp columns,
+    # the features zero-padded to a multiple of 8 (to_input_format)
+    input_dtype = torch.bfloat16
 
     @staticmethod
     def full_batch(device) -> int:
@@ -174,10 +176,6 @@ class NativeMLP:
         bf = torch.bfloat16
         self.Fp = _r8(n_features)
         self.X = torch.zeros(batch * self.Fp, dtype=bf, device=dev)
-        # the MFMA input format: the Trainer keeps resident datasets in it (half the bytes of
-        # fp32, and the per-step gather IS the engine's input: no cast kernel): bf16 rows of Fp
-        # columns, the features zero-padded to a multiple of 8 (to_input_format)
-        self.input_dtype = torch.bfloat16
         self._Xop = self.X  # the X operand of the current step (self.X or a bf16 batch read in place)
         self.Hs = [torch.empty(batch * h, dtype=bf, device=dev) for h in self.hidden]
         self.dZ = [torch.empty(batch * h, dtype=bf, device=dev) for h in self.hidden]
@@ -214,6 +212,7 @@ class NativeMLP:
         # transposed bf16 copy, written with the shadow); WELLFLOW_MLP_STEP128=0 (A/B,
         # tools/mlp_timeline.py): 64-row passes with W2^T in registers
         self.w2t = None
+        self.small = SmallLaunchState("NativeMLP")  # K steps per launch (fused_steps)
         if self.red is not None and self.dw2_frag and os.environ.get("WELLFLOW_MLP_STEP128", "1") != "0":
             self.w2t = torch.empty(256 * 256, dtype=bf, device=dev)
         self.sync_weights()
@@ -225,6 +224,19 @@ class NativeMLP:
         if self.w2t is None:
             return None
         return (self.w2t, self.lay.offsets()[0][1][0], 256, 256)
+
+    def fused_update_kwargs(self, kind: str) -> dict:  # Adam writes the shadow and W2^T in its own launch
+        return dict(shadow=self.shadow, shadow_t=self.shadow_t) if kind == "adam" else {}
+
+    def update_refreshes_operands(self, opt) -> bool:  # an Adam that writes ``shadow`` (and W2^T, if kept)
+        sh, ost = getattr(opt, "shadow", None), getattr(opt, "shadow_t", None)
+        return sh is self.shadow and (self.w2t is None or (ost is not None and ost[0] is self.w2t))
+
+    def gather_rows(self, src, order, out) -> None:
+        if src.is_contiguous() and (src[0].numel() * src.element_size()) % 4 == 0:
+            self._C.gather_rows(src, order, out)  # csrc/elementwise.hip gather_rows_kernel
+        else:
+            super().gather_rows(src, order, out)
 
     def sync_weights(self) -> None:
         self._C.cast_bf16(self.params, self.shadow)
@@ -427,9 +439,7 @@ class NativeMLP:
             # the launcher indexes rows with stride Fp: an [N][F] tensor with F < Fp would be misread
             raise RuntimeError(f"NativeMLP.fused_steps: X must be [N][{self.Fp}] (to_input_format), got "
                                f"{tuple(X.shape)}")
-        if getattr(self, "_small_scr", None) is None:
-            self._small_scr = torch.zeros(self._C.mlp_small_scratch_floats(), device=self.device)
-            self._small_sync = torch.zeros(4, dtype=torch.int32, device=self.device)
+        scr, sync = self.small.buffers(self._C.mlp_small_scratch_floats, self.device)
         (w1, b1), (w2, b2) = self.lay.offsets()[0]
         _, hw, hb, _ = self.lay.offsets()
         mae = self.loss_kind == "mae_clip"
@@ -441,21 +451,10 @@ class NativeMLP:
                                      rows, self.Fp, B, K, self.params, opt.m, opt.v, opt.step_dev, opt.lr, b1_, b2_,
                                      opt.eps, opt.weight_decay, (1.0 if mae else 2.0) * float(grad_scale),
                                      float(self.clip) if mae else 0.0, self.shadow, self.w2t, loss_into,
-                                     self._small_scr, self._small_sync, [w1, b1, w2, b2, hw, hb], stamps)
+                                     scr, sync, [w1, b1, w2, b2, hw, hb], stamps)
         if not ok:
             raise RuntimeError("NativeMLP.fused_steps: the launcher refused the shape")
         opt.t += K
-
-    def check_device_errors(self) -> None:
-        """Raise if a small-batch launch's hand-off timed out (sticky word; the buffer is reset)."""
-        sync = getattr(self, "_small_sync", None)
-        if sync is None:
-            return
-        err = int(sync[2].item())
-        if err:
-            sync.zero_()
-            raise RuntimeError("NativeMLP: a small-batch persistent launch timed out in a hand-off "
-                               "(results of that launch are invalid)")
 
     def forward_backward(self, x: torch.Tensor, y: torch.Tensor, grad_scale: float,
                          zero_grads: bool = True, step: int = 0, rows: torch.Tensor | None = None,

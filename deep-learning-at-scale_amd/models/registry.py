@@ -51,14 +51,14 @@ def build_engine(name: str, cfg, n_features: int, n_outputs: int, batch: int, de
 
 def engine_to_reference(eng, ref):
     """Copy the engine's current weights into the reference module (CPU)."""
-    if getattr(eng, "native", False):
+    if eng.native:
         ref.load_flat(eng.params.detach().cpu())
         return ref
     return eng.module
 
 
 def reference_to_engine(ref, eng) -> None:
-    if getattr(eng, "native", False):
+    if eng.native:
         eng.params.copy_(ref.to_flat().to(eng.params.device))
         eng.sync_weights()
     else:

@@ -15,7 +15,6 @@ import os
 import sys
 import time
 
-import numpy as np
 import torch
 
 from ..config import RunConfig, parse_argv
@@ -32,22 +31,16 @@ from .trainer import Trainer
 def _optimizer(cfg: RunConfig, eng):
     """The optimizer with the same launch fusions bench.py times: on a native engine the update
     also clears the gradient bucket (zero_grads), and it refreshes the engine's compute copies in
-    the same launch — NativeLSTM / NativeCNN through their fused writebacks, NativeMLP through
-    its bf16 shadow and the transposed W2 block — so no zero-fill or sync_weights launches run
-    per step (without them the MLP job's step ran ~17 % slower on the device than the bench's)."""
-    native = bool(getattr(eng, "native", False))
-    clip = dict(clipnorm=cfg.clipnorm, clipvalue=cfg.clipvalue)
-    if cfg.optimizer == "sgd":
+    the same launch (Engine.fused_update_kwargs: NativeLSTM / NativeCNN through their fused
+    writebacks, NativeMLP through its bf16 shadow and the transposed W2 block), so no zero-fill or
+    sync_weights launches run per step (without them the MLP job's step ran ~17 % slower on the
+    device than the bench's)."""
+    kind = "sgd" if cfg.optimizer == "sgd" else "adam"
+    kw = dict(clipnorm=cfg.clipnorm, clipvalue=cfg.clipvalue, zero_grads=eng.native, **eng.fused_update_kwargs(kind))
+    if kind == "sgd":
         return make_optimizer("sgd", eng.params, eng.grads, lr=cfg.lr, momentum=cfg.momentum,
-                              decay=cfg.decay, nesterov=cfg.nesterov, zero_grads=native,
-                              writeback=eng if hasattr(eng, "fused_sgd") else None, **clip)
-    kw = dict(clip)
-    if hasattr(eng, "fused_adam"):
-        kw["writeback"] = eng
-    elif native and getattr(eng, "shadow", None) is not None and hasattr(eng, "shadow_t"):
-        kw.update(shadow=eng.shadow, shadow_t=eng.shadow_t)  # NativeMLP
-    return make_optimizer("adam", eng.params, eng.grads, lr=cfg.lr, weight_decay=cfg.weight_decay,
-                          zero_grads=native, **kw)
+                              decay=cfg.decay, nesterov=cfg.nesterov, **kw)
+    return make_optimizer("adam", eng.params, eng.grads, lr=cfg.lr, weight_decay=cfg.weight_decay, **kw)
 
 
 def _save_best(cfg, name, ref, prepared):
@@ -176,7 +169,7 @@ def run_config(cfg: RunConfig, log=print) -> dict:
         trainer.fit(prepared.train, prepared.val)
     elapsed = time.time() - t0
     test_loss, test_mse = trainer.evaluate(*prepared.test)
-    trainer.check_device()  # running completion totals cover every persistent launch of the job
+    eng.check_device_errors()  # running completion totals cover every persistent launch of the job
     say("\nTime elapsed: %f s" % elapsed)  # cnn.py:133 (py3-correct)
     say("Testing set loss: %f" % test_loss)  # cnn.py:134
     result = {
@@ -185,9 +178,9 @@ def run_config(cfg: RunConfig, log=print) -> dict:
         "test_loss": test_loss, "test_mse": test_mse,
         "best_val_loss": trainer.stopper.best, "history": trainer.history.__dict__,
     }
-    if hasattr(eng, "persistent_stats"):  # csrc/persistent_guard.h totals (checked just above)
-        result["persistent"] = {k: {kk: vv for kk, vv in v.items() if kk != "first_exit"}
-                                for k, v in eng.persistent_stats().items()}
+    pstats = eng.persistent_stats()  # csrc/persistent_guard.h totals (checked just above)
+    if pstats:
+        result["persistent"] = {k: {kk: vv for kk, vv in v.items() if kk != "first_exit"} for k, v in pstats.items()}
     if ctx.is_main and os.environ.get("WELLFLOW_RESULT_JSON"):
         with open(os.environ["WELLFLOW_RESULT_JSON"], "w") as f:
             json.dump(result, f)

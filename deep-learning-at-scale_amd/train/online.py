@@ -22,8 +22,7 @@ import time
 
 import torch
 
-from ..models.base import CLIP_STEPS_REASON, note_slow_path
-from .trainer import _input_format, _to_dev
+from .trainer import _to_dev, small_steps_path
 
 
 def stream_chunks(X, Y, chunk: int):
@@ -151,9 +150,9 @@ def fit_online(trainer, train, val):
     chunk = max(cfg.online_chunk, ctx.world_size)
     passes = max(1, cfg.epochs)
     done_chunks = int(trainer.extra_state.get("chunks_done", 0))
-    streamed = eng.device.type == "cuda" and getattr(eng, "native", False)
+    streamed = eng.device.type == "cuda" and eng.native
     # this rank's rows of every chunk (the only rows it ever trains on), in arrival order
-    b_full = max(1, min(cfg.batch_size, getattr(eng, "B", cfg.batch_size)))
+    b_full = max(1, min(cfg.batch_size, eng.B or cfg.batch_size))
     Xs, Ys, table = rank_shard(Xtr, Ytr, chunk, ctx.rank, ctx.world_size, unit=b_full * ctx.world_size)
     streamer = None
     if streamed:
@@ -166,8 +165,8 @@ def fit_online(trainer, train, val):
         # input format (bf16 for the MLP: half the PCIe bytes), so a mini-batch is a pinned view
         # copied straight over PCIe (no per-batch host cast / staging memcpy, which held the
         # job at 0.68x the bench's streamed step)
-        Xs = _input_format(eng, torch.as_tensor(Xs))
-        Xs = (Xs if getattr(eng, "input_dtype", None) is not None else Xs.float()).pin_memory()
+        Xs = eng.to_input_format(torch.as_tensor(Xs))
+        Xs = (Xs if eng.input_dtype is not None else Xs.float()).pin_memory()
         Ys = torch.as_tensor(Ys).float().pin_memory()
     # the chunks still to run (resume skips those already consumed), in stream order
     plans, k = [], 0
@@ -183,16 +182,12 @@ def fit_online(trainer, train, val):
     # (NativeMLP.fused_steps through Trainer.train_steps(sliced=True)); the per-batch ring +
     # one-step graphs held the default job at 5.8 M rows/s
     staged = None
-    if (streamed and ctx.world_size == 1 and cfg.fail_at_step < 0 and plans
-            and getattr(eng, "small_steps_reason", None) is not None):
+    if streamed and plans:
         probe = torch.empty((b_full,) + tuple(Xs.shape[1:]), dtype=Xs.dtype, device=eng.device)
-        why = eng.small_steps_reason(b_full, trainer.opt, probe)
-        if why == CLIP_STEPS_REASON:  # checked last: clipping alone keeps the job off the K-step launch
-            note_slow_path(type(eng).__name__, "training runs one update per step, not K steps per launch",
-                           why, f"B={b_full}")
-        if why is None:
+        small, why = small_steps_path(eng, trainer.opt, ctx, cfg, b_full, probe)
+        if small:
             staged = _ChunkStage(Xs, Ys, max(pr for *_, pr in plans), eng.device)
-        elif cfg.verbose >= 1 and ctx.is_main:
+        elif why is not None and cfg.verbose >= 1 and ctx.is_main:
             trainer.log(f"Online: per-batch steps ({why})", flush=True)
     # the ring holds full batches of one shape: a chunk streams when this rank has >= 1 of them
     on_ring = [streamed and per_rank >= b_full for _, _, _, per_rank in plans]
@@ -230,7 +225,7 @@ def fit_online(trainer, train, val):
             Xd, Yd = _to_dev(Xr, eng.device), _to_dev(Yr, eng.device)
             order = torch.arange(0, per_rank, device=eng.device)
             tr_loss, rows, dt = trainer.train_steps(Xd, Yd, order, b)
-        trainer.check_device()
+        eng.check_device_errors()
         v_loss, v_mse = trainer.evaluate(*val)
         k += 1
         trainer.extra_state["chunks_done"] = k

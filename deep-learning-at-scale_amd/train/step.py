@@ -20,7 +20,6 @@ Round-1 verdict item 6 ("one step implementation for bench and jobs"): bench.py 
 """
 from __future__ import annotations
 
-import inspect
 import os
 import sys
 
@@ -46,25 +45,10 @@ class StepRunner:
         self.comm_in_graph = comm_in_graph if comm_in_graph is not None else _env_flag("WELLFLOW_COMM_IN_GRAPH", True)
         self.eager_steps = max(1, int(eager_steps))
         self.fused_clear = bool(getattr(opt, "zero_grads", False))
-        # Adam writing the engine's bf16 compute copy in its own launch (NativeMLP.shadow)
-        # replaces the separate repack
-        sh = getattr(opt, "shadow", None)
-        est, ost = getattr(eng, "shadow_t", None), getattr(opt, "shadow_t", None)
-        self.fused_shadow = (sh is not None and sh is getattr(eng, "shadow", None) and
-                             (est is None or (ost is not None and ost[0] is est[0])))
-        # ... or an optimizer whose writeback refreshes the engine's compute copies in its own
-        # launch — only when the engine's fused update covers THIS optimizer (the same predicate
-        # fused_adam / fused_sgd check: otherwise the plain update runs and sync_weights must follow)
-        if getattr(opt, "writeback", None) is eng:
-            ok = getattr(eng, "fused_adam_ok", None) or getattr(eng, "fused_sgd_ok", None)
-            if ok is not None and ok(opt):
-                self.fused_shadow = True
+        # the update refreshes the engine's compute copies in its own launch: no separate repack
+        self.fused_shadow = eng.update_refreshes_operands(opt)
+        # the engine adds the batch loss straight into the accumulator (no zero + add launches)
         self.loss_acc = torch.zeros(1, device=eng.device) if accumulate_loss else None
-        # engines that add the batch loss straight into the accumulator (no zero + add launches)
-        try:
-            self._loss_into = "loss_into" in inspect.signature(eng.forward_backward).parameters
-        except (TypeError, ValueError):
-            self._loss_into = False
         self.graphs: dict = {}
         self.update_graph = None  # comm outside the graph: [compute graph] all-reduce [update graph]
         self.calls = 0
@@ -72,19 +56,9 @@ class StepRunner:
 
     # ------------------------------------------------------------------ pieces
     def _compute(self, key):
-        inp = self.inputs(key)
-        kw = {"zero_grads": not self.fused_clear}
-        direct = self._loss_into and self.loss_acc is not None
-        if direct:
-            kw["loss_into"] = self.loss_acc
-        if len(inp) == 3:  # (dataset X, dataset y, row indices): the engine reads rows in place
-            x, y, rows = inp
-            ls = self.eng.forward_backward(x, y, self.grad_scale, rows=rows, **kw)
-        else:
-            x, y = inp
-            ls = self.eng.forward_backward(x, y, self.grad_scale, **kw)
-        if self.loss_acc is not None and not direct:
-            self.loss_acc += ls
+        x, y, *rows = self.inputs(key)  # (dataset X, dataset y, row indices): the engine reads rows in place
+        kw = {"rows": rows[0]} if rows else {}
+        self.eng.forward_backward(x, y, self.grad_scale, zero_grads=not self.fused_clear, loss_into=self.loss_acc, **kw)
 
     def _comm(self):
         self.ctx.all_reduce_sum_(self.eng.grads)
@@ -151,9 +125,8 @@ class StepRunner:
             g.replay()
             self._comm()
             self.update_graph.replay()
-        check = getattr(self.eng, "check_device_errors", None)
-        if check is not None and self.calls <= self.eager_steps + 1:
-            check()  # a broken hand-off in the first (eager / first replay) steps fails loudly
+        if self.calls <= self.eager_steps + 1:
+            self.eng.check_device_errors()  # a broken hand-off in the first (eager / first replay) steps fails loudly
 
     def _capture_many(self, key, n: int):
         """``n`` consecutive steps captured into ONE graph (step i reads ``inputs((key, i))``);
@@ -209,9 +182,8 @@ class StepRunner:
             first = False
         self.calls += n
         g.replay()
-        check = getattr(self.eng, "check_device_errors", None)
-        if first and check is not None:
-            check()
+        if first:
+            self.eng.check_device_errors()
 
     def take_loss(self) -> float:
         """Sum of per-sample losses since the last call (one host sync)."""

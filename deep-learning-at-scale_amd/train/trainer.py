@@ -28,7 +28,7 @@ import time
 import numpy as np
 import torch
 
-from ..models.base import per_element_loss
+from ..models.base import CLIP_STEPS_REASON, note_slow_path, per_element_loss
 from ..utils import checkpoint as ckpt
 from ..utils.profiling import trace_range
 
@@ -127,15 +127,18 @@ def _resident_windows(X, device) -> bool:
     return same and rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 2
 
 
-def _input_format(eng, Xd):
-    """A resident dataset in the engine's input format (``to_input_format``, else ``input_dtype``)."""
-    if not torch.is_tensor(Xd):
-        return Xd
-    fmt = getattr(eng, "to_input_format", None)
-    if fmt is not None:
-        return fmt(Xd)
-    in_dt = getattr(eng, "input_dtype", None)
-    return Xd.to(in_dt) if in_dt is not None and Xd.dtype != in_dt else Xd
+def small_steps_path(eng, opt, ctx, cfg, b: int, X):
+    """Whether batches of ``b`` rows of ``X`` may train K steps per persistent launch
+    (Engine.fused_steps) -> (eligible, the engine's reason; None when it was not asked): one
+    process (the update inside the launch has no all-reduce), no per-step fault injection, and
+    nothing against it from the engine. Clipping alone in the way (engines check it last) is said once."""
+    if ctx.world_size != 1 or cfg.fail_at_step >= 0:
+        return False, None
+    why = eng.small_steps_reason(b, opt, X)
+    if why == CLIP_STEPS_REASON:
+        note_slow_path(type(eng).__name__, "training runs one update per step, not K steps per launch",
+                       why, f"B={b}")
+    return why is None, why
 
 
 def _to_dev(a, device):
@@ -172,7 +175,7 @@ class Trainer:
         anything else comes back unchanged. Evaluating from host arrays cost ~220 ms per MLP
         epoch of 7 ms of training (a numpy gather + copy + two syncs per chunk)."""
         eng = self.eng
-        if not (getattr(eng, "native", False) and eng.device.type == "cuda"):
+        if not (eng.native and eng.device.type == "cuda"):
             return X, Y
         key = ("resident", id(X), id(Y))
         hit = self._idx.get(key)
@@ -183,7 +186,7 @@ class Trainer:
         if nbytes > torch.cuda.get_device_properties(eng.device).total_memory // 8:
             return X, Y  # a split this large stays on the host (chunked path)
         Xd, Yd = _to_dev(X, eng.device), _to_dev(Y, eng.device)  # windows: rows + starts on the device
-        Xd = _input_format(eng, Xd)
+        Xd = eng.to_input_format(Xd) if torch.is_tensor(Xd) else Xd  # (window sets stay as they are)
         self._idx[key] = (X, Y, Xd, Yd)
         return Xd, Yd
 
@@ -198,7 +201,7 @@ class Trainer:
         if torch.is_tensor(Y) and Y.device == dev and getattr(X, "device", None) == dev:
             return self._eval_device(X, Y, w, r, chunk)
         idx = np.arange(r, n, w)
-        chunk = chunk or getattr(self.eng, "B", 4096) or 4096
+        chunk = chunk or self.eng.B or 4096
         Xd = X if (torch.is_tensor(X) or hasattr(X, "starts")) and getattr(X, "device", None) == self.eng.device \
             else None
         pf = self._eval_prefetcher(X, chunk) if Xd is None and len(idx) > chunk else None
@@ -214,7 +217,7 @@ class Trainer:
         """Device-resident split: rank r's rows r, r + w, ... as strided slices (no gather; a
         window set gathers each chunk's windows on the GPU), the sums accumulated on the device
         and read back once."""
-        chunk = chunk or getattr(self.eng, "B", 4096) or 4096
+        chunk = chunk or self.eng.B or 4096
         windows = hasattr(X, "starts")  # device windows: each chunk gathered on the GPU
         ridx = torch.arange(r, len(X), w, device=Y.device) if windows else None
         Xr, Yr = (X, Y[r::w]) if windows else (X[r::w], Y[r::w])
@@ -293,9 +296,8 @@ class Trainer:
         """What the flat parameter vector means: its length and the engine's layout (e.g. the
         CNN's padded filter count), checked on resume (round-4 ADVICE: a layout change used to
         surface as a bare size mismatch inside params.copy_)."""
-        lay = getattr(self.eng, "lay", None) or getattr(self.eng, "layout", None)
         return {"engine": type(self.eng).__name__, "numel": int(self.eng.params.numel()),
-                "layout": repr(lay) if lay is not None else None}
+                "layout": repr(self.eng.lay) if self.eng.lay is not None else None}
 
     def load_state_dict(self, sd: dict) -> None:
         mine, theirs = self._layout_tag(), sd.get("layout")
@@ -307,7 +309,7 @@ class Trainer:
                 "configuration or an older flat layout; start without --resume (or remap the weights).")
         self.eng.params.copy_(sd["params"].to(self.eng.params.device))
         self.eng.sync_weights()
-        if getattr(self.eng, "rng", None) is not None:  # dropout stream continues where it stopped
+        if self.eng.rng is not None:  # dropout stream continues where it stopped
             self.eng.rng.fill_(int(sd["global_step"]))
         self.opt.load_state_dict(sd["optimizer"])
         self.epoch = int(sd["epoch"])
@@ -369,9 +371,8 @@ class Trainer:
         rk = (key, b)
         if self._runners.get("key") != rk:
             gscale = 1.0 / (b * self.ctx.world_size * self.n_out)
-            native = getattr(self.eng, "native", False)
             self._runners = {"key": rk, "run": StepRunner(self.eng, self.opt, self.ctx, gscale, make_inputs,
-                                                          graph=None if native else False)}
+                                                          graph=None if self.eng.native else False)}
         return self._runners["run"]
 
     def _after_step(self) -> bool:
@@ -405,8 +406,7 @@ class Trainer:
         engines on a GPU and while the copy takes under a quarter of the device's memory; None =
         keep gathering from the dataset in place."""
         eng = self.eng
-        if not (getattr(eng, "row_indexed", False) and torch.is_tensor(Xd) and torch.is_tensor(Yd)
-                and Xd.device.type == "cuda"):
+        if not (eng.row_indexed and torch.is_tensor(Xd) and torch.is_tensor(Yd) and Xd.device.type == "cuda"):
             return None
         m = len(order)
         need = m * (Xd[0].numel() * Xd.element_size() + Yd[0].numel() * Yd.element_size())
@@ -417,12 +417,8 @@ class Trainer:
         if bufs is None:
             bufs = self._idx[key] = (torch.empty((m,) + tuple(Xd.shape[1:]), dtype=Xd.dtype, device=Xd.device),
                                      torch.empty((m,) + tuple(Yd.shape[1:]), dtype=Yd.dtype, device=Yd.device))
-        C = getattr(eng, "_C", None)
-        for src, dst in ((Xd, bufs[0]), (Yd, bufs[1])):
-            if C is not None and src.is_contiguous() and (src[0].numel() * src.element_size()) % 4 == 0:
-                C.gather_rows(src, order, dst)  # csrc/elementwise.hip gather_rows_kernel
-            else:
-                torch.index_select(src, 0, order, out=dst)
+        eng.gather_rows(Xd, order, bufs[0])
+        eng.gather_rows(Yd, order, bufs[1])
         return bufs
 
     def train_steps(self, Xd, Yd, order: torch.Tensor, b: int, sliced: bool = False):
@@ -436,16 +432,16 @@ class Trainer:
         a fixed address per step, so every step's graph is captured once and no index is read."""
         eng, ctx = self.eng, self.ctx
         steps = len(order) // b
-        if steps == 0 and len(order) > 0 and not getattr(eng, "native", False):
+        if steps == 0 and len(order) > 0 and not eng.native:
             steps, b = 1, len(order)
         idx = self._idx.get(b)
         if idx is None:
             idx = self._idx[b] = torch.zeros(b, dtype=torch.long, device=eng.device)
 
-        row_indexed = getattr(eng, "row_indexed", False) and torch.is_tensor(Xd)
+        row_indexed = eng.row_indexed and torch.is_tensor(Xd)
         # resident windows (SeriesWindows on the device) that the engine reads in place through
         # the step's window ids (NativeLSTM: the x-pack kernel gathers them)
-        row_indexed = row_indexed or (getattr(eng, "window_indexed", False) and _resident_windows(Xd, eng.device))
+        row_indexed = row_indexed or (eng.window_indexed and _resident_windows(Xd, eng.device))
         # groups of n steps as ONE graph replay (StepRunner.run_many): step i of a group reads its
         # rows from slice i of a static order buffer filled by one copy per group; the per-step
         # index copy + replay gap (~8 us of a 165-us MLP step) goes away. Row-indexed engines,
@@ -483,18 +479,8 @@ class Trainer:
         prepared = False
         # small batches (the job defaults: MLP 256 rows, CNN 20 windows): up to
         # SMALL_STEPS_PER_LAUNCH complete steps — forward, backward AND the optimizer update — per
-        # persistent launch (NativeMLP / NativeCNN.fused_steps, csrc/mlp_small.hip, cnn_small.hip);
-        # one process (the update has no all-reduce)
-        small = (getattr(eng, "small_steps_reason", None) is not None and ctx.world_size == 1 and cfg.fail_at_step < 0
-                 and eng.small_steps_reason(b, self.opt, Xd) is None)
-        if (not small and getattr(self.opt, "clips", False) and ctx.world_size == 1 and cfg.fail_at_step < 0
-                and getattr(eng, "small_steps_reason", None) is not None):
-            from ..models.base import CLIP_STEPS_REASON, note_slow_path
-
-            # the reason checked last: a clipping optimizer is all that keeps this job off the K-step launch
-            if eng.small_steps_reason(b, self.opt, Xd) == CLIP_STEPS_REASON:
-                note_slow_path(type(eng).__name__, "training runs one update per step, not K steps per launch",
-                               CLIP_STEPS_REASON, f"B={b}")
+        # persistent launch (NativeMLP / NativeCNN.fused_steps, csrc/mlp_small.hip, cnn_small.hip)
+        small, _ = small_steps_path(eng, self.opt, ctx, cfg, b, Xd)
         while small and s < steps:
             clock.first()
             n = min(steps - s, SMALL_STEPS_PER_LAUNCH)
@@ -549,19 +535,13 @@ class Trainer:
         rows = done * b * ctx.world_size
         return tot / max(rows * self.n_out, 1), rows, dt
 
-    def check_device(self) -> None:
-        """Once per epoch: raise if a persistent kernel's hand-off timed out in any step."""
-        check = getattr(self.eng, "check_device_errors", None)
-        if check is not None:
-            check()
-
     def fit(self, train, val):
         cfg, ctx = self.cfg, self.ctx
         Xtr, Ytr = train
         dev = self.eng.device
         # resident dataset in device memory (288 GB HBM: the small well-log sets fit whole)
         Xd, Yd = _to_dev(Xtr, dev), _to_dev(Ytr, dev)
-        Xd = _input_format(self.eng, Xd)  # engine input format (NativeMLP: bf16 [N][Fp], read in place)
+        Xd = self.eng.to_input_format(Xd) if torch.is_tensor(Xd) else Xd  # (NativeMLP: bf16 [N][Fp], read in place)
         n = len(Xd)
         b = self._local_batch(n)
         per_rank = n // max(ctx.world_size, 1)
@@ -575,7 +555,7 @@ class Trainer:
                 Xs, Ys = Xd, Yd
             with trace_range("train_epoch", dev):
                 tr_loss, rows, dt = self.train_steps(Xs, Ys, order, b, sliced=src is not None)
-            self.check_device()
+            self.eng.check_device_errors()  # once per epoch: a hand-off timed out in some step
             with trace_range("evaluate", dev):
                 v_loss, v_mse = self.evaluate(*val)
             self.epoch += 1

@@ -402,7 +402,7 @@ def test_fused_steps_refuses_unpadded_rows():
         with pytest.raises(RuntimeError, match=r"X must be \[N\]\[8\]"):
             eng.fused_steps(bad, Y, B, 1, opt, 1.0 / B)
     torch.cuda.synchronize()
-    assert getattr(eng, "_small_scr", None) is None and opt.t == t0 and torch.equal(eng.params, p0)
+    assert eng.small.scratch is None and eng.small.sync is None and opt.t == t0 and torch.equal(eng.params, p0)
     eng.fused_steps(eng.to_input_format(X), Y, B, 1, opt, 1.0 / B)  # the input format is accepted
     torch.cuda.synchronize()
     eng.check_device_errors()

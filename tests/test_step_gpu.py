@@ -287,3 +287,78 @@ def test_run_many_with_rccl_group(monkeypatch, comm_in_graph):
         assert d <= 5e-5, d
     finally:
         ctx.shutdown()
+
+
+def test_update_fusion_decision_table(monkeypatch):
+    """Which optimizer update also refreshes the engine's operand copies (StepRunner.fused_shadow:
+    no sync_weights launch follows) and which kwargs the job's optimizer gets per engine
+    (train/job.py _optimizer), row by row as they were before the engines answered both questions
+    themselves. Only engines and optimizers are built; nothing trains."""
+    from wellflow.config import parse_argv
+    from wellflow.models.base import TorchEngine
+    from wellflow.models.cnn import CnnLayout, NativeCNN
+    from wellflow.models.lstm import NativeLSTM
+    from wellflow.models.mlp import MLPRegressor, NativeMLP
+    from wellflow.optim.flat import FlatAdam, FlatSGD
+    from wellflow.parallel.dist import DistContext
+    from wellflow.train import job
+    from wellflow.train.step import StepRunner
+
+    ctx = DistContext(device=torch.device(DEV))
+
+    def fused(eng, opt):
+        return StepRunner(eng, opt, ctx, 1.0, lambda k: (None, None)).fused_shadow
+
+    def adam(eng, **kw):
+        return FlatAdam(eng.params, eng.grads, **kw)
+
+    def sgd(eng, **kw):
+        return FlatSGD(eng.params, eng.grads, **kw)
+
+    mlp = NativeMLP(16, (256, 256), 64, device=DEV)
+    assert mlp.shadow_t is not None
+    assert fused(mlp, adam(mlp, shadow=mlp.shadow, shadow_t=mlp.shadow_t)) is True
+    assert fused(mlp, adam(mlp, shadow=mlp.shadow)) is False  # its transposed block would go stale
+    assert fused(mlp, adam(mlp)) is False
+    mlp1 = NativeMLP(13, (128,), 64, device=DEV)
+    assert mlp1.shadow_t is None
+    assert fused(mlp1, adam(mlp1, shadow=mlp1.shadow)) is True
+    lstm = NativeLSTM(9, 128, 2, 40, device=DEV)
+    assert fused(lstm, adam(lstm, writeback=lstm)) is True
+    assert fused(lstm, adam(lstm, writeback=lstm, shadow=torch.empty_like(lstm.params, dtype=torch.bfloat16))) is False
+    assert fused(lstm, adam(lstm)) is False
+    cnn = NativeCNN(CnnLayout(), 16, device=DEV)
+    assert cnn.fused
+    assert fused(cnn, sgd(cnn, writeback=cnn)) is True
+    assert fused(cnn, sgd(cnn)) is False
+    gemm_cnn = NativeCNN(CnnLayout(24, 3, 20, 5, 1), 16, device=DEV)
+    assert not gemm_cnn.fused
+    assert fused(gemm_cnn, sgd(gemm_cnn, writeback=gemm_cnn)) is False
+    # a writeback that is another engine instance refreshes that engine's copies, not this one's
+    assert fused(mlp, adam(mlp, writeback=NativeMLP(16, (256, 256), 64, device=DEV))) is False
+    assert fused(lstm, adam(lstm, writeback=NativeLSTM(9, 128, 2, 40, device=DEV))) is False
+    assert fused(cnn, sgd(cnn, writeback=NativeCNN(CnnLayout(), 16, device=DEV))) is False
+
+    got = {}
+
+    def spy(name, params, grads, **kw):
+        got.update(name=name, params=params, grads=grads, kw=kw)
+
+    monkeypatch.setattr(job, "make_optimizer", spy)
+    cfg = parse_argv("mlp", ["a", "float", "a", "/tmp/"])
+    torch_eng = TorchEngine(MLPRegressor(4, (8,)))
+    for eng in (mlp, mlp1, lstm, cnn, gemm_cnn, torch_eng):
+        native = eng is not torch_eng
+        for kind in ("sgd", "adam"):
+            cfg.optimizer = kind
+            job._optimizer(cfg, eng)
+            kw = got["kw"]
+            assert got["name"] == kind and got["params"] is eng.params and got["grads"] is eng.grads
+            assert kw["zero_grads"] is native
+            wb = isinstance(eng, NativeCNN) if kind == "sgd" else isinstance(eng, NativeLSTM)
+            assert (kw.get("writeback") is eng) if wb else (kw.get("writeback") is None), (type(eng).__name__, kind)
+            if kind == "adam" and isinstance(eng, NativeMLP):
+                assert kw["shadow"] is eng.shadow
+                assert kw["shadow_t"] is None if eng.w2t is None else kw["shadow_t"][0] is eng.w2t
+            else:
+                assert kw.get("shadow") is None and kw.get("shadow_t") is None

@@ -221,20 +221,21 @@ def test_writeback_skips_sync_only_when_the_fused_update_covers_the_optimizer():
     fell back to the plain update and trained on stale compute copies)."""
     import torch
 
+    from wellflow.models.base import Engine
     from wellflow.parallel.dist import DistContext
     from wellflow.train.step import StepRunner
 
-    class Eng:
+    class Eng(Engine):
         device = torch.device("cpu")
         grads = torch.zeros(4)
 
         def __init__(self, ok):
             self.ok = ok
 
-        def fused_adam_ok(self, opt):
+        def fused_update_ok(self, opt):
             return self.ok
 
-        def forward_backward(self, x, y, grad_scale, zero_grads=True):
+        def forward_backward(self, x, y, grad_scale, zero_grads=True, loss_into=None):
             return torch.zeros(1)
 
     class Opt:
@@ -248,3 +249,98 @@ def test_writeback_skips_sync_only_when_the_fused_update_covers_the_optimizer():
         eng = Eng(ok)
         run = StepRunner(eng, Opt(eng), DistContext(device="cpu"), 1.0, lambda k: (None, None), graph=False)
         assert run.fused_shadow is ok
+
+
+def test_torch_engine_satisfies_every_engine_default():
+    """TorchEngine adds nothing to the optional part of the contract: every capability flag,
+    attribute and method has the Engine default, and forward_backward takes ``loss_into`` with
+    the native engines' meaning (the batch loss added to the accumulator, which is returned)."""
+    from wellflow.models.base import Engine, TorchEngine
+    from wellflow.models.mlp import MLPRegressor
+    from wellflow.optim.flat import FlatAdam
+
+    torch.manual_seed(0)
+    eng = TorchEngine(MLPRegressor(5, (8, 8)))
+    assert isinstance(eng, Engine)
+    for name in ("native", "row_indexed", "window_indexed"):
+        assert getattr(eng, name) is False
+    for name in ("input_dtype", "B", "rng", "lay", "small", "writeback_update"):
+        assert getattr(eng, name) is None
+    for name in ("to_input_format", "gather_rows", "sync_weights", "check_device_errors", "persistent_stats",
+                 "small_steps_reason", "fused_steps", "fused_update_kwargs", "fused_update_ok",
+                 "update_refreshes_operands"):
+        assert getattr(type(eng), name) is getattr(Engine, name), name
+    X = torch.randn(6, 5)
+    assert eng.to_input_format(X) is X
+    out = torch.empty(3, 5)
+    eng.gather_rows(X, torch.tensor([4, 0, 2]), out)
+    assert torch.equal(out, X[[4, 0, 2]])
+    assert eng.sync_weights() is None and eng.check_device_errors() is None and eng.persistent_stats() == {}
+    opt = FlatAdam(eng.params, eng.grads)
+    why = eng.small_steps_reason(4, opt, X)
+    assert isinstance(why, str) and why
+    with pytest.raises(RuntimeError, match="TorchEngine.fused_steps: " + why):
+        eng.fused_steps(X, X[:, 0], 4, 1, opt, 1.0)
+    assert eng.fused_update_kwargs("adam") == {} and eng.fused_update_kwargs("sgd") == {}
+    assert eng.update_refreshes_operands(opt) is False
+    assert eng.update_refreshes_operands(FlatAdam(eng.params, eng.grads, writeback=eng)) is False
+    y = torch.randn(6)
+    ls = eng.forward_backward(X, y, 1.0 / 6)
+    g = eng.grads.clone()
+    acc = torch.full((1,), 2.0)
+    assert eng.forward_backward(X, y, 1.0 / 6, loss_into=acc) is acc
+    assert torch.equal(acc, 2.0 + ls) and torch.equal(eng.grads, g)
+
+
+def test_cpu_job_checkpoint_keeps_the_layout_tag(tmp_path):
+    """The .ckpt of a CPU job carries the layout tag this literal records (taken from a run before
+    the engines had a base class), so older checkpoints resume and newer ones read the same."""
+    from wellflow.train.job import run_job
+    from wellflow.utils.checkpoint import load_state
+
+    run_job("mlp", [NAMES, TYPES, "flow", str(tmp_path), "--epochs", "1", "--synth-wells", "3", "--synth-steps", "120",
+                    "--device", "cpu", "--batch-size", "32", "--verbose", "0"], log=lambda *a, **k: None)
+    st = load_state(str(tmp_path / "models" / "mlp.ckpt"))
+    assert st["layout"] == {"engine": "TorchEngine", "numel": 69633, "layout": None}
+
+
+def test_small_steps_path_eligibility(capfd, monkeypatch):
+    """train.trainer.small_steps_path, the one K-steps-per-launch decision of Trainer.train_steps
+    and fit_online: not eligible with two ranks, with fault injection (the engine is not even
+    asked) or when the engine has no such kernel; eligible when the engine has no objection; and
+    when clipping is the engine's only objection, that is said once however often it is asked."""
+    from wellflow.models import base
+    from wellflow.train.trainer import small_steps_path
+
+    monkeypatch.setattr(base, "_NOTED", set())
+    asked = []
+
+    class Eng(base.Engine):
+        def __init__(self, why):
+            self.why = why
+
+        def small_steps_reason(self, B, opt=None, X=None):
+            asked.append(B)
+            return self.why
+
+    def ctx(world):
+        return type("Ctx", (), {"world_size": world})()
+
+    def cfg(fail):
+        return type("Cfg", (), {"fail_at_step": fail})()
+
+    assert small_steps_path(Eng(None), None, ctx(1), cfg(-1), 32, None) == (True, None)
+    assert asked == [32]
+    assert small_steps_path(Eng(None), None, ctx(2), cfg(-1), 32, None) == (False, None)
+    assert small_steps_path(Eng(None), None, ctx(1), cfg(0), 32, None) == (False, None)
+    assert small_steps_path(Eng(None), None, ctx(1), cfg(7), 32, None) == (False, None)
+    assert asked == [32]  # more than one rank / fault injection: decided without the engine
+    ok, why = small_steps_path(base.Engine(), None, ctx(1), cfg(-1), 32, None)  # no kernel at all
+    assert ok is False and isinstance(why, str) and why
+    assert small_steps_path(Eng("batch 33"), None, ctx(1), cfg(-1), 33, None) == (False, "batch 33")
+    assert capfd.readouterr().err == ""
+    for _ in range(3):
+        assert small_steps_path(Eng(base.CLIP_STEPS_REASON), None, ctx(1), cfg(-1), 32, None) == \
+            (False, base.CLIP_STEPS_REASON)
+    err = capfd.readouterr().err
+    assert err.count(base.CLIP_STEPS_REASON) == 1 and "Eng" in err and "B=32" in err, err
