@@ -60,10 +60,88 @@ T* opt_ptr(const c10::optional<at::Tensor>& t, at::ScalarType dt, const char* na
   return reinterpret_cast<T*>(t->data_ptr());
 }
 
-// Extent of a logical [rows][K] operand stored K-contiguous or MN-contiguous.
-int64_t operand_extent(bool mn, int64_t rows, int64_t K, int64_t ld) {
-  if (rows == 0 || K == 0) return 0;
-  return mn ? (K - 1) * ld + rows : (rows - 1) * ld + K;
+// CPU tensors are accepted where nothing is launched (gemm_plan): the plan only needs sizes.
+void check_operand(const at::Tensor& t, at::ScalarType dt, const char* name, bool launch) {
+  if (launch) return check_t(t, dt, name);
+  TORCH_CHECK(t.defined(), name, ": undefined tensor");
+  TORCH_CHECK(t.scalar_type() == dt, name, ": expected dtype ", dt, " got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), name, ": must be contiguous");
+}
+
+template <class T>
+T* opt_operand(const c10::optional<at::Tensor>& t, at::ScalarType dt, const char* name, int64_t need, bool launch) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  check_operand(*t, dt, name, launch);
+  check_extent(*t, need, name);
+  return reinterpret_cast<T*>(t->data_ptr());
+}
+
+// Everything gemm checks and decides before its launch: the validated epilogue and whether the
+// direct-to-LDS ring may read these operands. gemm_plan runs exactly this and launches nothing.
+struct GemmCall {
+  wf::GemmEpilogue e;
+  bool glds_ok = false;
+};
+
+GemmCall gemm_prepare(const at::Tensor& A, bool a_mn, int64_t lda, const at::Tensor& B, bool b_mn, int64_t ldb,
+                      int64_t M, int64_t N, int64_t K, int64_t ksplit, const c10::optional<at::Tensor>& outF,
+                      const c10::optional<at::Tensor>& outH, int64_t ldo, const c10::optional<at::Tensor>& bias,
+                      const c10::optional<at::Tensor>& mask, int64_t ldm, double mask_scale,
+                      const c10::optional<at::Tensor>& colsum, double alpha, double beta, int64_t act, bool atomic,
+                      double drop_p, int64_t seed, int64_t big_tile, const c10::optional<at::Tensor>& seed_dev,
+                      bool launch) {
+  TORCH_CHECK(wf::dw_tile_valid(big_tile), "gemm: tile ", big_tile, " does not exist; valid ids are 0 (128x128), ",
+              "1 (256x128), 3 (256x192), 4 / 5 (256x192, 5- / 4-slot ring), 7 (best for N)");
+  check_operand(A, at::kBFloat16, "A", launch);
+  check_operand(B, at::kBFloat16, "B", launch);
+  TORCH_CHECK(M > 0 && N > 0 && K > 0, "gemm: empty problem");
+  TORCH_CHECK(lda % 8 == 0 && ldb % 8 == 0, "gemm: lda/ldb must be multiples of 8");
+  TORCH_CHECK(a_mn ? (M % 8 == 0) : (K % 8 == 0), "gemm: A contiguous extent must be a multiple of 8");
+  TORCH_CHECK(b_mn ? (N % 8 == 0) : (K % 8 == 0), "gemm: B contiguous extent must be a multiple of 8");
+  TORCH_CHECK(a_mn ? lda >= M : lda >= K, "gemm: lda too small");
+  TORCH_CHECK(b_mn ? ldb >= N : ldb >= K, "gemm: ldb too small");
+  check_extent(A, wf::gemm_operand_extent(a_mn, M, K, lda), "A");
+  check_extent(B, wf::gemm_operand_extent(b_mn, N, K, ldb), "B");
+  TORCH_CHECK(ldo >= N, "gemm: ldo < N");
+  // the epilogue's ranges: the kernel would take any other act as 0 and divide by 1 - drop_p
+  TORCH_CHECK(act == 0 || act == 1, "gemm: act must be 0 (linear) or 1 (ReLU), got ", act);
+  TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0, "gemm: drop_p must lie in [0, 1), got ", drop_p);
+  const int64_t out_need = (M - 1) * ldo + N;
+  GemmCall c;
+  wf::GemmEpilogue& e = c.e;
+  e.outF = opt_operand<float>(outF, at::kFloat, "outF", out_need, launch);
+  e.outH = opt_operand<bf16_t>(outH, at::kBFloat16, "outH", out_need, launch);
+  TORCH_CHECK(e.outF || e.outH, "gemm: need an output");
+  TORCH_CHECK(!atomic || (e.outF && !e.outH && beta == 0.0), "gemm: atomic needs outF only, beta 0");
+  TORCH_CHECK(beta == 0.0 || e.outF, "gemm: beta needs outF");
+  e.ldo = ldo;
+  e.bias = opt_operand<float>(bias, at::kFloat, "bias", N, launch);
+  if (mask.has_value() && mask->defined()) TORCH_CHECK(ldm >= N, "gemm: ldm < N");
+  e.mask = opt_operand<bf16_t>(mask, at::kBFloat16, "mask", (M - 1) * ldm + N, launch);
+  e.ldm = ldm;
+  e.mask_scale = (float)mask_scale;
+  e.colsum = opt_operand<float>(colsum, at::kFloat, "colsum", N, launch);
+  // the atomic epilogue adds alpha * acc and nothing else: refuse what it would silently drop
+  TORCH_CHECK(!atomic || (!e.bias && !e.mask && !e.colsum && act == 0 && drop_p == 0.0),
+              "gemm: atomic adds alpha * acc only; bias, mask, colsum, act and drop_p cannot go with it");
+  e.alpha = (float)alpha;
+  e.beta = (float)beta;
+  e.act = (int)act;
+  e.atomic = atomic ? 1 : 0;
+  e.drop_p = (float)drop_p;
+  e.seed = (unsigned long long)seed;
+  if (seed_dev.has_value() && seed_dev->defined()) {
+    TORCH_CHECK((seed_dev->is_cuda() || !launch) && seed_dev->scalar_type() == at::kLong && seed_dev->numel() >= 1,
+                "gemm: seed_dev must be a GPU int64 tensor");
+    e.seed_dev = reinterpret_cast<const long long*>(seed_dev->data_ptr<int64_t>());
+  }
+  e.big_tile = (int)big_tile;
+  TORCH_CHECK(ksplit == 1 || atomic, "gemm: split-K needs atomic accumulation");
+  e.stage_ok = wf::gemm_stage_ok(e.outF != nullptr, e.outH != nullptr, atomic, beta, N, ldo, e.mask != nullptr, ldm) ? 1 : 0;
+  // glds (whole-tile) path: the 128x128 tiles may over-read rows/cols past M / N; allow it
+  // only when that stays inside both allocations (and every K chunk is 64-aligned).
+  c.glds_ok = wf::gemm_glds_ok(a_mn, b_mn, M, N, K, lda, ldb, A.numel(), B.numel()) && !disable_glds();
+  return c;
 }
 
 void gemm(const at::Tensor& A, bool a_mn, int64_t lda, const at::Tensor& B, bool b_mn, int64_t ldb,
@@ -72,61 +150,32 @@ void gemm(const at::Tensor& A, bool a_mn, int64_t lda, const at::Tensor& B, bool
           c10::optional<at::Tensor> mask, int64_t ldm, double mask_scale,
           c10::optional<at::Tensor> colsum, double alpha, double beta, int64_t act, bool atomic,
           double drop_p, int64_t seed, int64_t big_tile, c10::optional<at::Tensor> seed_dev) {
-  TORCH_CHECK(wf::dw_tile_valid(big_tile), "gemm: tile ", big_tile, " does not exist; valid ids are 0 (128x128), ",
-              "1 (256x128), 3 (256x192), 4 / 5 (256x192, 5- / 4-slot ring), 7 (best for N)");
-  check_t(A, at::kBFloat16, "A");
-  check_t(B, at::kBFloat16, "B");
-  TORCH_CHECK(M > 0 && N > 0 && K > 0, "gemm: empty problem");
-  TORCH_CHECK(lda % 8 == 0 && ldb % 8 == 0, "gemm: lda/ldb must be multiples of 8");
-  TORCH_CHECK(a_mn ? (M % 8 == 0) : (K % 8 == 0), "gemm: A contiguous extent must be a multiple of 8");
-  TORCH_CHECK(b_mn ? (N % 8 == 0) : (K % 8 == 0), "gemm: B contiguous extent must be a multiple of 8");
-  TORCH_CHECK(a_mn ? lda >= M : lda >= K, "gemm: lda too small");
-  TORCH_CHECK(b_mn ? ldb >= N : ldb >= K, "gemm: ldb too small");
-  check_extent(A, operand_extent(a_mn, M, K, lda), "A");
-  check_extent(B, operand_extent(b_mn, N, K, ldb), "B");
-  TORCH_CHECK(ldo >= N, "gemm: ldo < N");
-  const int64_t out_need = (M - 1) * ldo + N;
-  wf::GemmEpilogue e;
-  e.outF = opt_ptr<float>(outF, at::kFloat, "outF", out_need);
-  e.outH = opt_ptr<bf16_t>(outH, at::kBFloat16, "outH", out_need);
-  TORCH_CHECK(e.outF || e.outH, "gemm: need an output");
-  TORCH_CHECK(!atomic || (e.outF && !e.outH && beta == 0.0), "gemm: atomic needs outF only, beta 0");
-  TORCH_CHECK(beta == 0.0 || e.outF, "gemm: beta needs outF");
-  e.ldo = ldo;
-  e.bias = opt_ptr<float>(bias, at::kFloat, "bias", N);
-  if (mask.has_value() && mask->defined()) TORCH_CHECK(ldm >= N, "gemm: ldm < N");
-  e.mask = opt_ptr<bf16_t>(mask, at::kBFloat16, "mask", (M - 1) * ldm + N);
-  e.ldm = ldm;
-  e.mask_scale = (float)mask_scale;
-  e.colsum = opt_ptr<float>(colsum, at::kFloat, "colsum", N);
-  e.alpha = (float)alpha;
-  e.beta = (float)beta;
-  e.act = (int)act;
-  e.atomic = atomic ? 1 : 0;
-  e.drop_p = (float)drop_p;
-  e.seed = (unsigned long long)seed;
-  if (seed_dev.has_value() && seed_dev->defined()) {
-    TORCH_CHECK(seed_dev->is_cuda() && seed_dev->scalar_type() == at::kLong && seed_dev->numel() >= 1,
-                "gemm: seed_dev must be a GPU int64 tensor");
-    e.seed_dev = reinterpret_cast<const long long*>(seed_dev->data_ptr<int64_t>());
-  }
-  e.big_tile = (int)big_tile;
-  TORCH_CHECK(ksplit == 1 || atomic, "gemm: split-K needs atomic accumulation");
-  e.stage_ok = (e.outH != nullptr && e.outF == nullptr && !atomic && beta == 0.0 && N % 8 == 0 &&
-                ldo % 8 == 0 && (e.mask == nullptr || ldm % 8 == 0))
-                   ? 1 : 0;
-  // glds (whole-tile) path: the 128x128 tiles may over-read rows/cols past M / N; allow it
-  // only when that stays inside both allocations (and every K chunk is 64-aligned).
-  const int64_t Mc = (M + 127) / 128 * 128, Nc = (N + 127) / 128 * 128;
-  int64_t kchunk = (K + std::max<int64_t>(ksplit, 1) - 1) / std::max<int64_t>(ksplit, 1);
-  kchunk = (kchunk + 63) / 64 * 64;
-  const bool glds_ok = (K % 64 == 0) && (kchunk % 64 == 0) &&
-                       A.numel() >= operand_extent(a_mn, Mc, K, lda) + (a_mn ? 0 : 0) &&
-                       B.numel() >= operand_extent(b_mn, Nc, K, ldb) &&
-                       (a_mn || Mc == M || lda >= K) && (b_mn || Nc == N || ldb >= K);
+  const GemmCall c = gemm_prepare(A, a_mn, lda, B, b_mn, ldb, M, N, K, ksplit, outF, outH, ldo, bias, mask, ldm,
+                                  mask_scale, colsum, alpha, beta, act, atomic, drop_p, seed, big_tile, seed_dev, true);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(A.device());
-  wf::launch_gemm(bfp(A), lda, a_mn, bfp(B), ldb, b_mn, (int)M, (int)N, (int)K, (int)ksplit, e,
-                  cur_stream(), glds_ok && !disable_glds());
+  wf::launch_gemm(bfp(A), lda, a_mn, bfp(B), ldb, b_mn, (int)M, (int)N, (int)K, (int)ksplit, c.e,
+                  cur_stream(), c.glds_ok);
+}
+
+// The route gemm takes for these arguments (kernels.h gemm_plan, the function launch_gemm itself
+// calls), after the same checks; nothing is launched, so CPU tensors of the same sizes will do.
+py::dict gemm_plan(const at::Tensor& A, bool a_mn, int64_t lda, const at::Tensor& B, bool b_mn, int64_t ldb,
+                   int64_t M, int64_t N, int64_t K, int64_t ksplit, c10::optional<at::Tensor> outF,
+                   c10::optional<at::Tensor> outH, int64_t ldo, c10::optional<at::Tensor> bias,
+                   c10::optional<at::Tensor> mask, int64_t ldm, double mask_scale,
+                   c10::optional<at::Tensor> colsum, double alpha, double beta, int64_t act, bool atomic,
+                   double drop_p, int64_t seed, int64_t big_tile, c10::optional<at::Tensor> seed_dev) {
+  const GemmCall c = gemm_prepare(A, a_mn, lda, B, b_mn, ldb, M, N, K, ksplit, outF, outH, ldo, bias, mask, ldm,
+                                  mask_scale, colsum, alpha, beta, act, atomic, drop_p, seed, big_tile, seed_dev, false);
+  const wf::GemmPlan p = wf::gemm_plan(a_mn, b_mn, (int)M, (int)N, (int)K, (int)ksplit, c.e, c.glds_ok);
+  py::dict d;
+  d["kernel"] = wf::gemm_kernel_name(p.kernel);
+  d["mainloop"] = p.ring ? "ring" : "register";
+  d["epilogue"] = p.staged ? "staged" : "direct";
+  d["kchunk"] = p.kchunk;
+  d["nsplit"] = p.nsplit;
+  d["workgroups"] = p.workgroups;
+  return d;
 }
 
 wf::LstmDims lstm_dims(int64_t B, int64_t T, int64_t F, int64_t KX, int64_t H) {
@@ -1575,6 +1624,7 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(solve_step);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
+  m.def("gemm_plan", &gemm_plan);
   m.def("cnn_fused_ok", &cnn_fused_ok);
   m.def("cnn_part_sizes", &cnn_part_sizes);
   WF_DEF(cnn_pack);

@@ -8,6 +8,17 @@
 // into the (pre-zeroed) fp32 output: the weight-gradient GEMMs here have tiny M x N
 // (<= 2048 x 576) and a huge K (batch x time), so the atomic bytes are <1% of the
 // MFMA time (cdna_hip_programming.md Guideline 12 sizing rule).
+//
+// Order of the epilogue: alpha * acc, + beta * out, + bias, ReLU, dropout, mask (> 0 keeps).
+// Pinned bit for bit by tests/test_gemm_exact_gpu.py, together with these three behaviours:
+//  * colsum sums what each epilogue has in hand. The staged bf16 epilogue (outH alone, N, ldo
+//    and ldm multiples of 8) sums the bf16-ROUNDED values it stores; the direct epilogue sums the
+//    UNROUNDED fp32 values, also when only outH is written. N = 128 and N = 132 therefore give
+//    bias gradients under different rules (the same numbers whenever the outputs are bf16 numbers).
+//  * the atomic (split-K) epilogue adds alpha * acc and nothing else: bias, act, mask, drop_p
+//    and colsum are refused by the binding together with atomic, not ignored.
+//  * act is 0 or 1 and drop_p lies in [0, 1): the binding refuses anything else.
+// Every host decision (kernel, mainloop, epilogue, K chunking, grid) is kernels.h gemm_plan.
 #include <cstdlib>
 
 #include "gemm_core.h"
@@ -152,20 +163,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const bf16_t* __rest
 
 template <int BM, int BN, int LA, int LB>
 static void launch_cfg(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-                       int ksplit, const GemmEpilogue& e, hipStream_t s, bool glds_ok) {
-  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  if (ksplit < 1) ksplit = 1;
-  int kchunk = (K + ksplit - 1) / ksplit;
-  kchunk = (kchunk + 63) / 64 * 64;
-  if (kchunk < 64) kchunk = 64;
-  const int nsplit = (K + kchunk - 1) / kchunk;
-  const dim3 grid(tiles * (nsplit > 0 ? nsplit : 1));
-  if (glds_ok && K % 64 == 0)
+                       const GemmPlan& p, const GemmEpilogue& e, hipStream_t s) {
+  const dim3 grid(p.workgroups);
+  if (p.ring)
     hipLaunchKernelGGL((gemm_kernel<BM, BN, LA, LB, 3>), grid, dim3(256), 0, s, A, lda, B, ldb, M,
-                       N, K, kchunk, e);
+                       N, K, p.kchunk, e);
   else
     hipLaunchKernelGGL((gemm_kernel<BM, BN, LA, LB, 0>), grid, dim3(256), 0, s, A, lda, B, ldb, M,
-                       N, K, kchunk, e);
+                       N, K, p.kchunk, e);
 }
 
 // ---- MN x MN split-K weight-gradient tiles (kernels.h DwTile) -------------------------------
@@ -182,13 +187,9 @@ static void launch_cfg(const bf16_t* A, long lda, const bf16_t* B, long ldb, int
 // 256x128, 8 waves, 3-stage glds ring (144 KiB): 87 FLOP per staged byte instead of 64 for
 // 128x128. Takes any N (the generic epilogue masks the last column tile).
 static void launch_dw_big(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-                          int ksplit, const GemmEpilogue& e, hipStream_t s) {
-  constexpr int BM = 256, BN = 128;
-  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  int kchunk = ((K + ksplit - 1) / ksplit + 63) / 64 * 64;
-  const int nsplit = (K + kchunk - 1) / kchunk;
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, MN_CONTIG, MN_CONTIG, 3, 4, 2>), dim3(tiles * nsplit),
-                     dim3(512), 0, s, A, lda, B, ldb, M, N, K, kchunk, e);
+                          const GemmPlan& p, const GemmEpilogue& e, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_kernel<256, 128, MN_CONTIG, MN_CONTIG, 3, 4, 2>), dim3(p.workgroups),
+                     dim3(512), 0, s, A, lda, B, ldb, M, N, K, p.kchunk, e);
 }
 
 // Split-K weight-gradient kernel: MN x MN operands, full tiles only (M % BM == N % BN == 0,
@@ -217,26 +218,16 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dw_kernel(const bf16_t* __r
         atomicAdd(out + (size_t)cc.row(i, r) * ldo + cc.col(j), alpha * acc[i][j][r]);
 }
 
-// equal 64-aligned K chunks (K % (64 * nsplit) == 0 is required: partial chunks would need the
-// masked mainloop)
-static int equal_ksplit(int K, int ksplit) {
-  int nsplit = ksplit;
-  while (nsplit > 1 && K % (64 * nsplit) != 0) --nsplit;
-  return nsplit;
-}
-
 // 256x192, 8 waves of 64x96, 2-stage ring (112 KiB): N = 576 = 3 x 192 exactly, and 22 % fewer
 // operand bytes per MFMA than 256x128 (rotation-swizzled 192-wide MN image). s_setprio(1) around
 // each MFMA cluster (cdna_hip_programming.md §5.5 T5: hipcc then keeps the clusters between the
 // barriers): 1.24 -> 1.16 ms at B = 8192.
-static void launch_dw_192(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-                          int ksplit, const GemmEpilogue& e, hipStream_t s) {
+static void launch_dw_192(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N,
+                          const GemmPlan& p, const GemmEpilogue& e, hipStream_t s) {
   constexpr int BM = 256, BN = 192;
   const int tiles = (M / BM) * (N / BN);
-  const int nsplit = equal_ksplit(K, ksplit);
-  const int kchunk = K / nsplit;
-  hipLaunchKernelGGL((gemm_dw_kernel<BM, BN, 2, 4, 2, 1>), dim3(tiles * nsplit), dim3(512), 0, s, A, lda, B, ldb,
-                     N, kchunk, tiles, e.outF, e.ldo, e.alpha);
+  hipLaunchKernelGGL((gemm_dw_kernel<BM, BN, 2, 4, 2, 1>), dim3(p.workgroups), dim3(512), 0, s, A, lda, B, ldb,
+                     N, p.kchunk, tiles, e.outF, e.ldo, e.alpha);
 }
 
 // The same contract as gemm_dw_kernel with BKD-deep steps through an NSLOT-deep ring
@@ -279,18 +270,16 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dw_h_kernel(const bf16_t* _
 
 // The 256x192 tile of launch_dw_192 through the half-step ring, its DMA issued NSLOT - 1 half
 // steps ahead instead of one 64-deep step (kDw256x192Ring5 / Ring4, A/B only)
-static void launch_dw_192h(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-                           int ksplit, int nslot, const GemmEpilogue& e, hipStream_t s) {
+static void launch_dw_192h(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N,
+                           const GemmPlan& p, const GemmEpilogue& e, hipStream_t s) {
   constexpr int BM = 256, BN = 192;
   const int tiles = (M / BM) * (N / BN);
-  const int nsplit = equal_ksplit(K, ksplit);
-  const int kchunk = K / nsplit;
-  const dim3 grid(tiles * nsplit);
-  if (nslot == 5)
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 5, 4, 2, 1>), grid, dim3(512), 0, s, A, lda, B, ldb, N, kchunk,
+  const dim3 grid(p.workgroups);
+  if (p.nslot == 5)
+    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 5, 4, 2, 1>), grid, dim3(512), 0, s, A, lda, B, ldb, N, p.kchunk,
                        tiles, e.outF, e.ldo, e.alpha, nullptr, 0L);
   else
-    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1>), grid, dim3(512), 0, s, A, lda, B, ldb, N, kchunk,
+    hipLaunchKernelGGL((gemm_dw_h_kernel<BM, BN, 4, 4, 2, 1>), grid, dim3(512), 0, s, A, lda, B, ldb, N, p.kchunk,
                        tiles, e.outF, e.ldo, e.alpha, nullptr, 0L);
 }
 
@@ -316,24 +305,26 @@ __global__ __launch_bounds__(256) void dw_slab_reduce_kernel(float* __restrict__
   reinterpret_cast<float4*>(out)[i] = a;
 }
 
-// 256x288, 8 waves of 64x144, 4-slot 32-deep ring (136 KiB; a 2-stage 64-deep ring spilled 61
-// VGPRs): N = 576 = 2 x 288, 24 % more FLOP per staged byte than 256x192 (1.107 vs 1.166 ms
-// standalone, 1.150 vs 1.178 ms inside the bench step). s_setprio(1) around each MFMA cluster.
-static void launch_dw_288w(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-                           int ksplit, const GemmEpilogue& e, hipStream_t s) {
-  constexpr int BM = 256, BN = 288;
-  const int tiles = (M / BM) * (N / BN);
-  // one workgroup per CU: 16 tiles x split-K 16 on 256 CUs (tools/dw_tiles.py, B = 8192:
-  // split-K 16 / 32 / 64 = 1.107 / 1.115 / 1.160 ms)
+// The 256x288 tile runs one workgroup per CU: the plan (kernels.h gemm_plan) caps its split-K by
+// this count.
+int gemm_dw288_cus() {
   static const int cus = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       return 256;
     return n;
   }();
-  if (ksplit * tiles > cus && cus / tiles >= 1) ksplit = cus / tiles;
-  const int nsplit = equal_ksplit(K, ksplit);
-  const int kchunk = K / nsplit;
+  return cus;
+}
+
+// 256x288, 8 waves of 64x144, 4-slot 32-deep ring (136 KiB; a 2-stage 64-deep ring spilled 61
+// VGPRs): N = 576 = 2 x 288, 24 % more FLOP per staged byte than 256x192 (1.107 vs 1.166 ms
+// standalone, 1.150 vs 1.178 ms inside the bench step). s_setprio(1) around each MFMA cluster.
+static void launch_dw_288w(const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N,
+                           const GemmPlan& p, const GemmEpilogue& e, hipStream_t s) {
+  constexpr int BM = 256, BN = 288;
+  const int tiles = (M / BM) * (N / BN);
+  const int nsplit = p.nsplit, kchunk = p.kchunk;
   // split-K partials: fp32 atomics into the output (2048 x 576 x 16 splits = 75 MB of 64-B-segment
   // atomics at the tail of the kernel) or, given a slab, plain stores + one reduce
   const long mn = (long)M * N;
@@ -349,28 +340,23 @@ static void launch_dw_288w(const bf16_t* A, long lda, const bf16_t* B, long ldb,
 
 void launch_gemm(const bf16_t* A, long lda, int a_mn, const bf16_t* B, long ldb, int b_mn, int M,
                  int N, int K, int ksplit, const GemmEpilogue& e, hipStream_t s, bool glds_ok) {
-  // the weight-gradient tiles: whole 256-row tiles of MN x MN operands, whole 64-deep K steps,
-  // the whole-tile over-read allowed by the host, atomic epilogue
-  if (a_mn && b_mn && glds_ok && e.atomic && e.big_tile != kDwGeneric && M % 256 == 0 && K % 64 == 0) {
-    const int ks = ksplit < 1 ? 1 : ksplit;
-    if (e.big_tile == kDwBest && N % 288 == 0)
-      launch_dw_288w(A, lda, B, ldb, M, N, K, ks, e, s);
-    else if ((e.big_tile == kDw256x192Ring5 || e.big_tile == kDw256x192Ring4) && N % 192 == 0)
-      launch_dw_192h(A, lda, B, ldb, M, N, K, ks, e.big_tile == kDw256x192Ring5 ? 5 : 4, e, s);
-    else if (e.big_tile != kDw256x128 && N % 192 == 0)  // e.g. H = 128 (KA = 192)
-      launch_dw_192(A, lda, B, ldb, M, N, K, ks, e, s);
-    else  // e.g. H = 256 (KA = 320)
-      launch_dw_big(A, lda, B, ldb, M, N, K, ks, e, s);
-    return;
+  // every host decision (kernel, mainloop, K chunking, grid) is kernels.h gemm_plan
+  const GemmPlan p = gemm_plan(a_mn, b_mn, M, N, K, ksplit, e, glds_ok);
+  switch (p.kernel) {
+    case kGemmDw256x288: launch_dw_288w(A, lda, B, ldb, M, N, p, e, s); return;
+    case kGemmDw256x192h: launch_dw_192h(A, lda, B, ldb, M, N, p, e, s); return;
+    case kGemmDw256x192: launch_dw_192(A, lda, B, ldb, M, N, p, e, s); return;
+    case kGemmDw256x128: launch_dw_big(A, lda, B, ldb, M, N, K, p, e, s); return;
+    default: break;
   }
   if (!a_mn && !b_mn)
-    launch_cfg<128, 128, K_CONTIG, K_CONTIG>(A, lda, B, ldb, M, N, K, ksplit, e, s, glds_ok);
+    launch_cfg<128, 128, K_CONTIG, K_CONTIG>(A, lda, B, ldb, M, N, K, p, e, s);
   else if (!a_mn && b_mn)
-    launch_cfg<128, 128, K_CONTIG, MN_CONTIG>(A, lda, B, ldb, M, N, K, ksplit, e, s, glds_ok);
+    launch_cfg<128, 128, K_CONTIG, MN_CONTIG>(A, lda, B, ldb, M, N, K, p, e, s);
   else if (a_mn && !b_mn)
-    launch_cfg<128, 128, MN_CONTIG, K_CONTIG>(A, lda, B, ldb, M, N, K, ksplit, e, s, glds_ok);
+    launch_cfg<128, 128, MN_CONTIG, K_CONTIG>(A, lda, B, ldb, M, N, K, p, e, s);
   else
-    launch_cfg<128, 128, MN_CONTIG, MN_CONTIG>(A, lda, B, ldb, M, N, K, ksplit, e, s, glds_ok);
+    launch_cfg<128, 128, MN_CONTIG, MN_CONTIG>(A, lda, B, ldb, M, N, K, p, e, s);
 }
 
 }  // namespace wf

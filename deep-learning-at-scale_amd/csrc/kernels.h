@@ -49,6 +49,108 @@ void launch_gemm(const bf16_t* A, long lda, int a_mn, const bf16_t* B, long ldb,
                  int N, int K, int ksplit, const GemmEpilogue& e, hipStream_t s,
                  bool glds_ok = false);
 
+// ---- the GEMM's host decisions, in one place: launch_gemm (gemm.hip) and the bindings' gemm /
+// gemm_plan (binding.cpp) all call these, so what gemm_plan reports is what a launch does.
+
+// Extent of a logical [rows][K] operand stored K-contiguous or MN-contiguous.
+inline long gemm_operand_extent(bool mn, long rows, long K, long ld) {
+  if (rows == 0 || K == 0) return 0;
+  return mn ? (K - 1) * ld + rows : (rows - 1) * ld + K;
+}
+// The bf16 output (and mask) tiles may go through LDS as whole 16-B row segments.
+inline bool gemm_stage_ok(bool has_outF, bool has_outH, bool atomic, double beta, long N, long ldo, bool has_mask,
+                          long ldm) {
+  return has_outH && !has_outF && !atomic && beta == 0.0 && N % 8 == 0 && ldo % 8 == 0 && (!has_mask || ldm % 8 == 0);
+}
+// The direct-to-LDS ring reads whole 128 x 64 tiles: rows / columns past M / N up to the next
+// multiple of 128 must lie inside both allocations (a_numel / b_numel elements), and K must be
+// whole 64-deep steps.
+inline bool gemm_glds_ok(bool a_mn, bool b_mn, long M, long N, long K, long lda, long ldb, long a_numel,
+                         long b_numel) {
+  const long Mc = (M + 127) / 128 * 128, Nc = (N + 127) / 128 * 128;
+  return K % 64 == 0 && a_numel >= gemm_operand_extent(a_mn, Mc, K, lda) &&
+         b_numel >= gemm_operand_extent(b_mn, Nc, K, ldb) && (a_mn || Mc == M || lda >= K) &&
+         (b_mn || Nc == N || ldb >= K);
+}
+
+enum GemmKernelId : int { kGemmGeneric = 0, kGemmDw256x128, kGemmDw256x192, kGemmDw256x192h, kGemmDw256x288 };
+inline const char* gemm_kernel_name(int k) {
+  switch (k) {
+    case kGemmDw256x128: return "dw256x128";
+    case kGemmDw256x192: return "dw256x192";
+    case kGemmDw256x192h: return "dw256x192h";
+    case kGemmDw256x288: return "dw256x288";
+    default: return "generic";
+  }
+}
+struct GemmPlan {
+  int kernel = kGemmGeneric;  // GemmKernelId
+  int ring = 0;               // 1: direct-to-LDS ring mainloop, 0: register-staged
+  int staged = 0;             // 1: bf16 epilogue through LDS, 0: direct
+  int nslot = 0;              // kGemmDw256x192h: ring slots (5 or 4)
+  int kchunk = 0, nsplit = 1, workgroups = 0;
+};
+// CU count the 256x288 tile sizes its split-K by (gemm.hip; 256 when no device answers)
+int gemm_dw288_cus();
+
+// equal 64-aligned K chunks of the 256-row tiles (K % (64 * nsplit) == 0 is required: partial
+// chunks would need the masked mainloop); gemm.hip's equal_ksplit before the plan moved here
+inline int gemm_equal_ksplit(int K, int ksplit) {
+  int nsplit = ksplit;
+  while (nsplit > 1 && K % (64 * nsplit) != 0) --nsplit;
+  return nsplit;
+}
+
+// Which kernel, mainloop and epilogue launch_gemm runs for these arguments, and its K chunking
+// and grid. glds_ok: gemm_glds_ok of the operands (and no WELLFLOW_NO_GLDS).
+inline GemmPlan gemm_plan(int a_mn, int b_mn, int M, int N, int K, int ksplit, const GemmEpilogue& e, bool glds_ok) {
+  GemmPlan p;
+  // the weight-gradient tiles: whole 256-row tiles of MN x MN operands, whole 64-deep K steps,
+  // the whole-tile over-read allowed by the host, atomic epilogue
+  if (a_mn && b_mn && glds_ok && e.atomic && e.big_tile != kDwGeneric && M % 256 == 0 && K % 64 == 0) {
+    int ks = ksplit < 1 ? 1 : ksplit;
+    p.ring = 1;
+    if (e.big_tile == kDwBest && N % 288 == 0) {
+      p.kernel = kGemmDw256x288;
+    } else if ((e.big_tile == kDw256x192Ring5 || e.big_tile == kDw256x192Ring4) && N % 192 == 0) {
+      p.kernel = kGemmDw256x192h;
+      p.nslot = e.big_tile == kDw256x192Ring5 ? 5 : 4;
+    } else if (e.big_tile != kDw256x128 && N % 192 == 0) {  // e.g. H = 128 (KA = 192)
+      p.kernel = kGemmDw256x192;
+    } else {  // e.g. H = 256 (KA = 320)
+      p.kernel = kGemmDw256x128;
+    }
+    if (p.kernel == kGemmDw256x128) {  // any N: the generic epilogue masks the last column tile
+      const int tiles = ((M + 255) / 256) * ((N + 127) / 128);
+      p.kchunk = ((K + ks - 1) / ks + 63) / 64 * 64;
+      p.nsplit = (K + p.kchunk - 1) / p.kchunk;
+      p.workgroups = tiles * p.nsplit;
+      return p;
+    }
+    const int bn = p.kernel == kGemmDw256x288 ? 288 : 192;
+    const int tiles = (M / 256) * (N / bn);
+    if (p.kernel == kGemmDw256x288) {
+      // one workgroup per CU: 16 tiles x split-K 16 on 256 CUs (tools/dw_tiles.py, B = 8192:
+      // split-K 16 / 32 / 64 = 1.107 / 1.115 / 1.160 ms)
+      const int cus = gemm_dw288_cus();
+      if (ks * tiles > cus && cus / tiles >= 1) ks = cus / tiles;
+    }
+    p.nsplit = gemm_equal_ksplit(K, ks);
+    p.kchunk = K / p.nsplit;
+    p.workgroups = tiles * p.nsplit;
+    return p;
+  }
+  const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
+  if (ksplit < 1) ksplit = 1;
+  p.kchunk = ((K + ksplit - 1) / ksplit + 63) / 64 * 64;
+  if (p.kchunk < 64) p.kchunk = 64;
+  p.nsplit = (K + p.kchunk - 1) / p.kchunk;
+  p.workgroups = tiles * (p.nsplit > 0 ? p.nsplit : 1);
+  p.ring = (glds_ok && K % 64 == 0) ? 1 : 0;
+  p.staged = (e.stage_ok && e.outH != nullptr && e.outF == nullptr && !e.atomic) ? 1 : 0;
+  return p;
+}
+
 // ---- LSTM (single layer, batch-first input, seq-to-one regression) ----
 struct LstmDims {
   int B, T, F, KX, H;  // G = 4H, KA = KX + H

@@ -431,7 +431,40 @@ def gemm(A, B, M, N, K, *, a_mn=False, lda=None, b_mn=False, ldb=None, outF=None
     4-slot half-step ring (A/B), 7 = the best for N (256x288, else 256x192, else 256x128). Any
     other id raises; a shape the tile cannot take runs as 0.
     ``seed_dev`` (int64 GPU tensor): a device step counter mixed into the dropout seed.
+
+    Order of the epilogue: ``alpha * acc``, ``+ beta * out``, ``+ bias``, ReLU (``act`` 1),
+    dropout (``drop_p`` in [0, 1), key ``m * N + n``), mask (``mask > 0`` keeps, times
+    ``mask_scale``). ``outF`` and ``outH`` may be given together; ``outH`` is rounded to nearest
+    even. Pinned bit for bit by tests/test_gemm_exact_gpu.py, with these rules:
+
+    * ``colsum[n] +=`` the column sums of what the epilogue has in hand: the staged bf16 epilogue
+      (``outH`` alone, ``beta`` 0, ``N``, ``ldo`` and ``ldm`` multiples of 8) sums the
+      bf16-ROUNDED values it stores, the direct epilogue (every other call) the UNROUNDED fp32
+      values, also when only ``outH`` is written. The two agree whenever the outputs are bf16
+      numbers; :func:`gemm_plan` tells which one a call takes.
+    * ``atomic`` adds ``alpha * acc`` into ``outF`` and nothing else: ``bias``, ``mask``,
+      ``colsum``, ``act`` and ``drop_p`` raise together with it (they used to be ignored).
+    * ``act`` outside {0, 1} and ``drop_p`` outside [0, 1) raise.
     """
+    lib().gemm(*_gemm_args(A, B, M, N, K, a_mn, lda, b_mn, ldb, outF, outH, ldo, bias, mask, ldm, mask_scale, colsum,
+                           alpha, beta, act, atomic, ksplit, drop_p, seed, tile, seed_dev))
+
+
+def gemm_plan(A, B, M, N, K, *, a_mn=False, lda=None, b_mn=False, ldb=None, outF=None, outH=None,
+              ldo=None, bias=None, mask=None, ldm=None, mask_scale=1.0, colsum=None, alpha=1.0,
+              beta=0.0, act=0, atomic=False, ksplit=1, drop_p=0.0, seed=0, tile=0, seed_dev=None) -> dict:
+    """The route :func:`gemm` takes for the same arguments, after the same checks, without a
+    launch: ``kernel`` ("generic", "dw256x128", "dw256x192", "dw256x192h", "dw256x288"),
+    ``mainloop`` ("ring" = direct-to-LDS, "register"), ``epilogue`` ("staged", "direct"),
+    ``kchunk``, ``nsplit``, ``workgroups``. It is the function the launcher itself calls
+    (csrc/kernels.h gemm_plan). Tensors on the CPU are accepted: only their sizes count."""
+    return lib().gemm_plan(*_gemm_args(A, B, M, N, K, a_mn, lda, b_mn, ldb, outF, outH, ldo, bias, mask, ldm,
+                                       mask_scale, colsum, alpha, beta, act, atomic, ksplit, drop_p, seed, tile,
+                                       seed_dev))
+
+
+def _gemm_args(A, B, M, N, K, a_mn, lda, b_mn, ldb, outF, outH, ldo, bias, mask, ldm, mask_scale, colsum, alpha,
+               beta, act, atomic, ksplit, drop_p, seed, tile, seed_dev) -> tuple:
     if lda is None:
         lda = M if a_mn else K
     if ldb is None:
@@ -440,6 +473,6 @@ def gemm(A, B, M, N, K, *, a_mn=False, lda=None, b_mn=False, ldb=None, outF=None
         ldo = N
     if ldm is None:
         ldm = ldo
-    lib().gemm(A, bool(a_mn), int(lda), B, bool(b_mn), int(ldb), int(M), int(N), int(K),
-               int(ksplit), outF, outH, int(ldo), bias, mask, int(ldm), float(mask_scale), colsum,
-               float(alpha), float(beta), int(act), bool(atomic), float(drop_p), int(seed), int(tile), seed_dev)
+    return (A, bool(a_mn), int(lda), B, bool(b_mn), int(ldb), int(M), int(N), int(K), int(ksplit), outF, outH,
+            int(ldo), bias, mask, int(ldm), float(mask_scale), colsum, float(alpha), float(beta), int(act),
+            bool(atomic), float(drop_p), int(seed), int(tile), seed_dev)
