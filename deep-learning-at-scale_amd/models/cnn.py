@@ -304,6 +304,8 @@ class NativeCNN(Engine):
         """K complete training steps (forward with the engine's dropout stream, backward, the
         Keras SGD update of ``opt``) in ONE launch. Step k reads windows ``rows[k B : (k + 1) B]``
         of ``X`` ([N][48] fp32) / ``Y`` ([N][outputs]), or windows k B .. when ``rows`` is None.
+        The kernel clamps every row id into [0, N): an id below 0 reads window 0, one at or above
+        N reads window N - 1 (never an out-of-bounds read; no host check, which would need a sync).
         ``loss_into`` += each step's loss sum. The gradient bucket is not written; the bf16
         operand images are refreshed after the launch. Equals K single steps of this path bit for
         bit (tests/test_small_gpu.py)."""

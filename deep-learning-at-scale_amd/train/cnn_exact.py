@@ -32,6 +32,14 @@ Also here: the bit-for-bit host mirror of the GEMM epilogue's dropout
 (:func:`gemm_dropout_mask`), host encoders of the three bf16 operand images of the fused kernels
 from their documented layout (:func:`cnn_images`), the float64 Keras SGD step
 (:func:`keras_sgd_fp64`) and the comparator the tests share (:func:`block_mismatches`).
+
+K-step launches of the small-batch kernel: after one update the parameters leave the lattice, so
+two live steps cannot be exact. A launch in which ONE step has a nonzero gradient can: the other
+batches are *dead* (clipped MAE, every residual far beyond the clip: loss B * outputs * clip, dOut
+zero whatever the parameters) or *still* (MSE, targets = the prediction under that step's own
+mask: everything zero, before the live step only). :func:`cnn_launch_fp64` replays such a launch,
+:func:`cnn_launch_violations` proves it exact; the momentum then carries the live step's velocity
+through the steps that follow, every intermediate an fp32 number.
 """
 from __future__ import annotations
 
@@ -93,6 +101,10 @@ def exact_cnn_case(layout: CnnLayout, B: int, seed: int, loss: str = "mse", drop
     # the residuals every problem must hold: a zero, the clip boundary from both sides and one
     # beyond it (a problem of fewer than four elements gets one with a gradient instead)
     plant = (0.0, 1.0, 2.0 if loss == "mae_clip" else 0.5, -1.0)
+    if B * O == len(plant) and loss == "mae_clip":
+        # four elements in all: +1 and -1 would cancel in the dense-bias gradient (one output: the
+        # sum of sign(e) over the batch), so the fourth is one within the clip
+        plant = plant[:3] + (0.5,)
     if B * O >= len(plant):
         e.view(-1)[: len(plant)] = torch.tensor(plant, dtype=torch.float64)
     else:
@@ -253,9 +265,9 @@ def cnn_exactness_violations(case: CnnExactCase, y: torch.Tensor, mask: torch.Te
         dAct, dWd, dWc with its bias row, the dense-bias gradient, the loss sum) the sum of
         |terms| stays below 2^24 quanta of its terms, so any partial sum in any order is an fp32
         number;
-    (d) with ``sgd`` = {"lr", "momentum", "nesterov"} (the small-batch kernel, which applies the
-        Keras update itself from zero velocities): lr * g, the new velocities and the new
-        parameters are sums of fewer than 2^24 quanta and survive the fp32 round trip."""
+    (d) with ``sgd`` = {"lr", "momentum", "nesterov"} and optionally {"decay", "iteration",
+        "velocities"} (the small-batch kernel, which applies the Keras update itself; zero decay,
+        counter and velocities unless given): :func:`sgd_update_violations` finds nothing."""
     bad: list = []
     lay, ks = case.lay, case.keep_scale
     B = case.x.shape[0]
@@ -303,14 +315,153 @@ def cnn_exactness_violations(case: CnnExactCase, y: torch.Tensor, mask: torch.Te
     _sum_ok("gbd", dout.abs().sum(0), quantum(dout), bad)
     _sum_ok("loss_sum", ref["per"].abs().sum().reshape(1), quantum(ref["per"]), bad)
     if sgd is not None:
-        lr, mu = sgd["lr"], sgd["momentum"]
-        g = ref["grads"]
-        zero = torch.zeros_like(g)
-        pn, vn = keras_sgd_fp64(case.flat, g, zero, lr, mu, sgd["nesterov"])
-        for name, t in (("lr * g", lr * g), ("new velocities", vn), ("new parameters", pn)):
-            _roundtrip_ok(name, t, f32, bad)
-        terms = case.flat.abs() + (mu + 1.0) * lr * g.abs()
-        _sum_ok("SGD update", terms, min(quantum(case.flat), mu * lr * quantum(g)), bad)
+        vel = sgd.get("velocities")
+        vel = torch.zeros_like(ref["grads"]) if vel is None else vel
+        sgd_update_violations(case.flat, ref["grads"], vel, sgd, sgd.get("iteration", 0), bad)
+    return bad
+
+
+def sgd_lr_t_fp32(lr: float, decay: float, iteration: float) -> float:
+    """``lr / (1.f + decay * it)`` as the small kernel forms it: three fp32 operations on fp32 values."""
+    t = lambda v: torch.tensor(float(v), dtype=torch.float32)  # noqa: E731
+    return float(t(lr) / (t(1.0) + t(decay) * t(iteration)))
+
+
+def sgd_update_violations(p: torch.Tensor, g: torch.Tensor, v: torch.Tensor, sgd: dict, iteration: int, bad: list,
+                          tag: str = "") -> None:
+    """Condition (d) of :func:`cnn_exactness_violations` for one Keras step from parameters ``p``,
+    gradient ``g`` and velocities ``v`` (float64) at step counter ``iteration``: with a nonzero
+    gradient the kernel's fp32 ``lr_t`` is the float64 one; ``momentum * v``, ``lr_t * g``, the new
+    velocities, ``momentum * v'``, the Nesterov sum and the new parameters are fp32 numbers (so
+    each operation's exact result is representable, fused into a multiply-add or not) and the
+    update sums fewer than 2^24 quanta."""
+    f32 = torch.float32
+    lr, mu, decay = sgd["lr"], sgd["momentum"], sgd.get("decay", 0.0)
+    lr_t = lr / (1.0 + decay * iteration)
+    if bool((g != 0).any()) and sgd_lr_t_fp32(lr, decay, iteration) != lr_t:
+        bad.append(f"{tag}lr_t: fp32 gives {sgd_lr_t_fp32(lr, decay, iteration)!r}, float64 {lr_t!r}")
+    pn, vn = keras_sgd_fp64(p, g, v, lr, mu, sgd["nesterov"], decay, iteration)
+    for name, t in (("momentum * v", mu * v), ("lr * g", lr_t * g), ("new velocities", vn), ("momentum * v'", mu * vn),
+                    ("momentum * v' - lr * g", mu * vn - lr_t * g), ("new parameters", pn)):
+        _roundtrip_ok(tag + name, t, f32, bad)
+    terms = p.abs() + (mu + 1.0) * (mu * v.abs() + lr_t * g.abs())
+    q = min(quantum(p), mu * lr_t * quantum(g), mu * mu * quantum(v))
+    _sum_ok(tag + "SGD update", terms, q, bad)
+
+
+# ------------------------------------------------------------------- K-step launches, replayed
+DEAD_OFFSET = 64.0    # a dead batch's targets: the float64 prediction +- this (far beyond CLIP)
+DEAD_MARGIN = 32.0    # every |pred - y| of a dead step must stay above this in the replay
+VEL_VALUES = (-0.5, -0.375, -0.25, -0.125, 0.0, 0.125, 0.25, 0.375, 0.5)
+
+
+def lattice_velocities(lay: CnnLayout, seed: int) -> torch.Tensor:
+    """Velocities on the lattice (multiples of 1/8 in [-0.5, 0.5]) for every live parameter, zero
+    on all padding: float64 [lay.numel]."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    flat = torch.zeros(lay.numel, dtype=torch.float64)
+    Wc, Wd, bd = lay.views(flat)
+    F, O = lay.filters, lay.outputs
+    Wc[:F, : lay.taps + 1] = _pick(VEL_VALUES, (F, lay.taps + 1), g)
+    Wd.view(lay.Op, lay.lout, lay.Fp)[:O, :, :F] = _pick(VEL_VALUES, (O, lay.lout, F), g)
+    bd[:O] = _pick(VEL_VALUES, (O,), g)
+    return flat
+
+
+def _train_pred(flat, x, mask, keep_scale, lay) -> torch.Tensor:
+    B = x.shape[0]
+    zero = torch.zeros(B, lay.outputs, dtype=torch.float64)
+    return cnn_step_fp64(flat, x, zero, 0.0, "mse", CLIP, mask, keep_scale, lay)["pred"][:, : lay.outputs]
+
+
+def still_targets(flat, x, mask, keep_scale: float, lay: CnnLayout) -> torch.Tensor:
+    """Targets of a *still* MSE batch: the float64 training prediction under this step's own mask,
+    so every residual, the loss and every gradient are exactly 0 (while ``flat`` is what the step
+    starts from; under any other mask the step is live)."""
+    return _train_pred(flat, x, mask, keep_scale, lay)
+
+
+def dead_targets(flat, x, mask, keep_scale: float, lay: CnnLayout, seed: int) -> torch.Tensor:
+    """Targets of a *dead* clipped-MAE batch: the float64 prediction from ``flat`` (the parameters
+    the step starts from, on the lattice or not) +- DEAD_OFFSET, signs drawn from ``seed``,
+    rounded to fp32. Every residual is far beyond the clip, so the loss sum is B * outputs * clip
+    and dOut is zero however the kernel rounds its prediction."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    pred = _train_pred(flat, x, mask, keep_scale, lay)
+    return (pred + DEAD_OFFSET * _pick((-1.0, 1.0), tuple(pred.shape), g)).float().double()
+
+
+def cnn_launch_fp64(flat: torch.Tensor, vel: torch.Tensor, steps, grad_scale: float, loss: str, clip: float,
+                    keep_scale: float, lay: CnnLayout, sgd: dict, it0: int = 0) -> dict:
+    """A K-step launch of the small-batch kernel replayed in float64. ``steps``: K tuples (x, y,
+    mask), the mask being that of device step ``rng0 + k`` (None without dropout). Step k is
+    :func:`cnn_step_fp64` on batch k from the current parameters, then :func:`keras_sgd_fp64` with
+    ``iteration = it0 + k`` (``sgd``: lr, momentum, nesterov, decay). Returns ``params``,
+    ``velocities``, ``loss_sum`` (summed over the steps) and ``trace``: per step the state it
+    started from (``params``, ``velocities``), its ``ref`` (the cnn_step_fp64 dict) and ``loss``."""
+    p, v = flat.double().clone(), vel.double().clone()
+    total = torch.zeros((), dtype=torch.float64)
+    trace = []
+    for k, (x, y, mask) in enumerate(steps):
+        ref = cnn_step_fp64(p, x, y, grad_scale, loss, clip, mask, keep_scale, lay)
+        trace.append({"params": p, "velocities": v, "ref": ref, "loss": ref["loss_sum"]})
+        p, v = keras_sgd_fp64(p, ref["grads"], v, sgd["lr"], sgd["momentum"], sgd["nesterov"], sgd.get("decay", 0.0),
+                              it0 + k)
+        total = total + ref["loss_sum"]
+    return {"params": p, "velocities": v, "loss_sum": total, "trace": trace}
+
+
+def cnn_launch_violations(case: CnnExactCase, vel: torch.Tensor, steps, kinds, sgd: dict, it0: int, clip: float = CLIP,
+                          loss0: float = 0.0) -> list:
+    """Why the small-batch kernel could legitimately differ from :func:`cnn_launch_fp64` on a
+    launch with ONE live step (``kinds``: "live", "dead" or "still" per step; ``case`` holds the
+    parameters, grad_scale, loss and dropout; the live batch is steps[k_live]). Empty when
+
+    * every step up to the live one, and every still step, starts from ``case.flat`` and passes
+      :func:`cnn_exactness_violations` (the live one with its Keras update from the velocities and
+      step counter it meets);
+    * every still step has residuals, loss and gradients exactly 0; every dead step has all
+      |pred - y| > DEAD_MARGIN (a clipped-MAE launch), loss B * outputs * clip and zero gradients;
+    * every step's update passes :func:`sgd_update_violations` (so every intermediate parameter
+      and velocity is an fp32 number), every target is one, and the loss accumulated from
+      ``loss0`` is one after every step."""
+    bad: list = []
+    lay, ks = case.lay, case.keep_scale
+    if list(kinds).count("live") != 1:
+        return [f"kinds {kinds}: exactly one live step expected"]
+    k_live = list(kinds).index("live")
+    run = cnn_launch_fp64(case.flat, vel, steps, case.grad_scale, case.loss, clip, ks, lay, sgd, it0)
+    acc = float(loss0)
+    for k, ((x, y, mask), kind, tr) in enumerate(zip(steps, kinds, run["trace"])):
+        tag = f"step {k} ({kind}): "
+        ref = tr["ref"]
+        B = x.shape[0]
+        _roundtrip_ok(tag + "y", y, torch.float32, bad)
+        if k <= k_live or kind == "still":
+            if not torch.equal(tr["params"], case.flat.double()):
+                bad.append(tag + "does not start from the lattice parameters")
+            ck = CnnExactCase(lay, tr["params"], x, case.e, case.grad_scale, case.loss, case.dropout)
+            live_sgd = dict(sgd, velocities=tr["velocities"], iteration=it0 + k) if kind == "live" else None
+            bad += [tag + v for v in cnn_exactness_violations(ck, y, mask, "small", clip, live_sgd)]
+        d = ref["pred"][:, : lay.outputs] - y
+        if kind == "still":
+            if case.loss != "mse" or bool((d != 0).any()) or float(ref["loss_sum"]) != 0.0:
+                bad.append(tag + "a residual is not 0")
+        if kind == "dead":
+            if case.loss != "mae_clip" or not float(d.abs().min()) > max(DEAD_MARGIN, 2 * clip):
+                bad.append(tag + f"a residual within {DEAD_MARGIN} of the clip")
+            if float(ref["loss_sum"]) != B * lay.outputs * clip:
+                bad.append(tag + f"loss {float(ref['loss_sum'])!r} is not B * outputs * clip")
+        if kind != "live" and bool((ref["grads"] != 0).any()):
+            bad.append(tag + "a gradient is not 0")
+        if kind == "live" and not all(bool((b != 0).any()) for b in lay.views(ref["grads"])):
+            bad.append(tag + "a gradient block of the live step is all zero")
+        sgd_update_violations(tr["params"], ref["grads"], tr["velocities"], sgd, it0 + k, bad, tag)
+        acc += float(ref["loss_sum"])
+        if float(torch.tensor(acc, dtype=torch.float32)) != acc:
+            bad.append(tag + f"accumulated loss {acc!r} is no fp32 number")
+    for name in ("params", "velocities"):
+        _roundtrip_ok(f"final {name}", run[name], torch.float32, bad)
     return bad
 
 
@@ -341,6 +492,8 @@ def step_blocks(ref: dict, lay: CnnLayout, mult: float = 1.0) -> dict:
     return {"dout": ref["dout"].float(), "loss": ref["loss_sum"].reshape(1).float(), "gWc": gWc, "gWd": gWd, "gbd": gbd}
 
 
-__all__ = ["CLIP", "MAX_QUANTA", "CnnExactCase", "block_mismatches", "cnn_exactness_violations", "cnn_forward_fp64",
-           "cnn_grad_scale", "cnn_images", "cnn_step_fp64", "exact_cnn_case", "exact_cnn_targets", "gemm_dropout_mask",
-           "keras_sgd_fp64", "seed32", "step_blocks", "uniform_hash"]
+__all__ = ["CLIP", "DEAD_MARGIN", "DEAD_OFFSET", "MAX_QUANTA", "CnnExactCase", "block_mismatches",
+           "cnn_exactness_violations", "cnn_forward_fp64", "cnn_grad_scale", "cnn_images", "cnn_launch_fp64",
+           "cnn_launch_violations", "cnn_step_fp64", "dead_targets", "exact_cnn_case", "exact_cnn_targets",
+           "gemm_dropout_mask", "keras_sgd_fp64", "lattice_velocities", "seed32", "sgd_lr_t_fp32", "sgd_update_violations",
+           "step_blocks", "still_targets", "uniform_hash"]

@@ -8,7 +8,11 @@
 * both dropout mirrors and the three operand-image encoders equal per-element loops;
 * planted errors in a host replica of the fused step (organised as the kernels are: 16-window
   groups, backward chunks, the operand images) are each rejected by the comparator the GPU tests
-  use.
+  use;
+* the small-batch kernel's edge layouts reach the branches they are listed for, its preset-state
+  steps and its K-step launches with one live step are exact and covering, the float64 replay of
+  a launch equals K calls of the one-step reference, and planted errors in that replay are each
+  rejected by every launch listed for them.
 """
 import importlib.util
 import math
@@ -395,3 +399,178 @@ def test_keras_sgd_fp64_matches_flat_sgd():
         pn, vn = cx.keras_sgd_fp64(p, 0.5 * gr, v, 0.25, 0.5, nesterov)
         torch.testing.assert_close(opt.params, pn, rtol=1e-14, atol=1e-15)
         torch.testing.assert_close(opt.vel, vn, rtol=1e-14, atol=1e-15)
+
+
+# ------------------------------------------------- the small-batch kernel: layouts, state, K steps
+def test_small_kernel_layouts_reach_the_listed_branches():
+    """The launcher's arithmetic (csrc/cnn_small.hip launch_cnn_small and the kernel's hop 1) for
+    every (layout, B) of test_cnn_small_kernel_one_step: G = 25 / 27 / 28 workgroups, a last
+    workgroup with ONE live filter at 97 / 105 / 109 filters, workers without a hop-1 output
+    (nout < G) at one output and B = 4 / 20, a second trip of the hop-1 loop (nl * G > 1024) at 16
+    outputs and B = 64 with both G; never more than 48 outputs per worker (red2's rows)."""
+    seen = {}
+    for lay_t in GPU.SMALL_LAYS:
+        for B in GPU.SMALL_B:
+            br = GPU.small_branches(lay_t, B)
+            seen[(lay_t[2], lay_t[4], B)] = br
+            assert br["G"] <= 28 and -(-br["nout"] // br["G"]) <= 48 and 4 * br["G"] <= 112
+    assert {k[0]: v["G"] for k, v in seen.items()} == {97: 25, 100: 25, 105: 27, 109: 28, 112: 28}
+    assert {k[0] for k, v in seen.items() if v["one_live_filter"]} == {97, 105, 109}
+    assert {k for k, v in seen.items() if v["idle_workers"]} == {(97, 1, 4), (97, 1, 20), (109, 1, 4), (109, 1, 20)}
+    assert {k for k, v in seen.items() if v["second_trip"]} == {(100, 16, 64), (112, 16, 64)}
+    assert seen[(100, 16, 64)]["G"] * 41 == 1025 and seen[(112, 16, 64)]["G"] * 37 == 1036
+    assert not seen[(100, 12, 64)]["second_trip"]  # the reference layout tops out at 768 outputs
+
+
+@pytest.mark.parametrize("key", GPU.STATE_KEYS, ids=lambda k: f"F{k[0][2]}-O{k[0][4]}-B{k[1]}-{k[2]}-nesterov{k[3]}")
+def test_preset_state_steps_are_exact_and_covering(key):
+    """test_cnn_small_kernel_step_from_preset_state: from lattice velocities, counter 16 and decay
+    2^-4 the step is exact; the velocities are live everywhere and zero on the padding; the
+    carried velocity, the counter (15 and 17 give another lr_t, and no fp32-exact one) and the
+    momentum rule each change the expected result."""
+    lay_t, B, loss, nesterov = key
+    prob = GPU.problem(lay_t, B, loss, 0.5, "small")
+    lay, g, flat = prob.lay, prob.ref["grads"], prob.case.flat
+    vel = GPU.state_velocities(prob)
+    sgd = GPU.state_sgd(nesterov, vel)
+    assert cx.cnn_exactness_violations(prob.case, prob.y, prob.mask, "small", cx.CLIP, sgd) == []
+    F, O = lay.filters, lay.outputs
+    Wc, Wd, bd = lay.views(vel)
+    assert Wc[F:].abs().sum() == 0 and Wc[:, lay.taps + 1:].abs().sum() == 0 and bd[O:].abs().sum() == 0
+    assert Wd[O:].abs().sum() == 0 and Wd.view(lay.Op, lay.lout, lay.Fp)[:, :, F:].abs().sum() == 0
+    assert all(set((8 * b).reshape(-1).tolist()) >= {-4.0, 4.0, 1.0} for b in (Wc, Wd)) and bool((bd != 0).any())
+    lr, mu = sgd["lr"], sgd["momentum"]
+    assert cx.sgd_lr_t_fp32(lr, GPU.DECAY_STATE, GPU.IT_STATE) == lr / 2
+    want = cx.keras_sgd_fp64(flat, g, vel, lr, mu, nesterov, GPU.DECAY_STATE, GPU.IT_STATE)
+    for other in (cx.keras_sgd_fp64(flat, g, vel, lr, mu, nesterov, GPU.DECAY_STATE, GPU.IT_STATE - 1),
+                  cx.keras_sgd_fp64(flat, g, vel, lr, mu, nesterov, GPU.DECAY_STATE, GPU.IT_STATE + 1),
+                  cx.keras_sgd_fp64(flat, g, vel, lr, mu, nesterov, 0.0, GPU.IT_STATE),
+                  cx.keras_sgd_fp64(flat, g, vel * 0, lr, mu, nesterov, GPU.DECAY_STATE, GPU.IT_STATE),
+                  cx.keras_sgd_fp64(flat, g, vel, lr, mu, not nesterov, GPU.DECAY_STATE, GPU.IT_STATE)):
+        for i, block in enumerate(lay.views(other[0].float())):   # every parameter block would show it
+            assert not torch.equal(block, lay.views(want[0].float())[i])
+    for it in (GPU.IT_STATE - 1, GPU.IT_STATE + 1):
+        bad = cx.cnn_exactness_violations(prob.case, prob.y, prob.mask, "small", cx.CLIP, dict(sgd, iteration=it))
+        assert any("lr_t" in v for v in bad)
+
+
+def _sched_blocks(lay, p, v, loss_sum):
+    """Parameters, velocities and the loss as the fp32 blocks the GPU test compares."""
+    out = {"loss": (GPU.LOSS0 + loss_sum).reshape(1).float()}
+    for i, name in enumerate(("Wc", "Wd", "bd")):
+        out[f"{name} params"], out[f"{name} velocities"] = lay.views(p.float())[i], lay.views(v.float())[i]
+    return out
+
+
+LAUNCH_MUTATIONS = {
+    # name -> which schedules (key: layout, B, loss, dropout, kinds, nesterov, preset, contiguous) MUST reject it
+    "every_step_draws_the_mask_of_rng0": lambda k: k[3] > 0 and k[4].index("live") > 0,
+    "lr_t_from_it0_for_every_step": lambda k: k[4].index("live") > 0,
+    "step_k_reads_the_rows_of_step_k_minus_1": lambda k: k[4].index("live") > 0,
+    "launch_velocities_taken_as_zero": lambda k: k[6],
+    "momentum_not_applied_on_a_zero_gradient_step": lambda k: k[6] or k[4].index("live") < len(k[4]) - 1,
+    "nesterov_and_plain_momentum_swapped": lambda k: True,
+    "dead_step_loss_dropped": lambda k: "dead" in k[4],
+}
+
+
+def _launch_by_hand(s, mut=None):
+    """The launch as K calls of the one-step reference and the Keras step, written out here
+    (not through cnn_launch_fp64); ``mut`` plants one error."""
+    c, lay = s.case, s.lay
+    lr, mu, decay = s.sgd["lr"], s.sgd["momentum"], s.sgd["decay"]
+    nesterov = s.sgd["nesterov"] != (mut == "nesterov_and_plain_momentum_swapped")
+    p = c.flat.clone()
+    v = torch.zeros_like(p) if mut == "launch_velocities_taken_as_zero" else s.vel0.clone()
+    total = torch.zeros((), dtype=torch.float64)
+    for k, (x, y, mask) in enumerate(s.steps):
+        if mut == "every_step_draws_the_mask_of_rng0":
+            mask = s.steps[0][2]
+        if mut == "step_k_reads_the_rows_of_step_k_minus_1" and k > 0:
+            x, y = s.steps[k - 1][0], s.steps[k - 1][1]
+        ref = cx.cnn_step_fp64(p, x, y, c.grad_scale, s.loss, cx.CLIP, mask, c.keep_scale, lay)
+        g = ref["grads"]
+        it = s.it0 if mut == "lr_t_from_it0_for_every_step" else s.it0 + k
+        if mut == "momentum_not_applied_on_a_zero_gradient_step" and not bool((g != 0).any()):
+            p = p + (mu * v if nesterov else v)
+        else:
+            p, v = cx.keras_sgd_fp64(p, g, v, lr, mu, nesterov, decay, it)
+        if not (mut == "dead_step_loss_dropped" and s.kinds[k] == "dead"):
+            total = total + ref["loss_sum"]
+    return _sched_blocks(lay, p, v, total)
+
+
+@pytest.mark.parametrize("key", GPU.SCHEDULES, ids=GPU._sched_id)
+def test_one_live_step_schedules_are_exact_and_covering(key):
+    """Every launch of test_cnn_small_kernel_one_live_step: proved exact (every intermediate
+    parameter and velocity of every step an fp32 number, the live step's gradient blocks all
+    nonzero, each dead step's loss B * outputs * CLIP, each still step all zeros); the replay
+    equals K calls of the one-step reference; and the launch holds what it is listed for."""
+    s = GPU.schedule(key)
+    assert s.violations() == []
+    lay, B, K, kl = s.lay, s.B, s.K, s.k_live
+    run = s.run
+    want = _sched_blocks(lay, run["params"], run["velocities"], run["loss_sum"])
+    assert cx.block_mismatches(_launch_by_hand(s), want) == []
+    gpu_want = GPU.small_want(lay, run["params"], run["velocities"], run["loss_sum"], s.it0 + K, K)
+    assert all(torch.equal(gpu_want[k], want[k]) for k in want)
+    assert float(run["loss_sum"]) == float(run["trace"][kl]["loss"]) + s.kinds.count("dead") * B * lay.outputs * cx.CLIP
+    # lr_t is lr / 2 at the live step's counter and at no other step of the launch
+    lr, decay = s.sgd["lr"], s.sgd["decay"]
+    assert s.it0 + kl == GPU.IT_STATE
+    assert [cx.sgd_lr_t_fp32(lr, decay, s.it0 + k) == lr / 2 for k in range(K)] == [k == kl for k in range(K)]
+    # distinct batches, and a table whose other rows hold other data
+    for a in range(K):
+        for b in range(a + 1, K):
+            assert not torch.equal(s.steps[a][0], s.steps[b][0]) and not torch.equal(s.steps[a][1], s.steps[b][1])
+    X, Y, rows = s.table()
+    if s.contiguous:
+        assert rows is None and X.shape[0] == K * B
+    else:
+        assert X.shape[0] == (K + 2) * B and rows.unique().numel() == K * B and not torch.equal(rows, rows.sort().values)
+        for k in range(K):
+            assert torch.equal(X[rows[k * B : (k + 1) * B]], s.steps[k][0].reshape(B, -1))
+            assert torch.equal(Y[rows[k * B : (k + 1) * B]], s.steps[k][1])
+    if s.p > 0:   # each step has a mask of its own
+        assert all(not torch.equal(s.steps[a][2], s.steps[a + 1][2]) for a in range(K - 1))
+    # after the live step the velocity decays by the momentum once per step and the parameters move
+    mu = s.sgd["momentum"]
+    tr = run["trace"]
+    for k in range(kl + 1, K):
+        assert torch.equal(tr[k]["velocities"] * mu, tr[k + 1]["velocities"] if k + 1 < K else run["velocities"])
+        assert not torch.equal(tr[k]["params"], tr[k + 1]["params"] if k + 1 < K else run["params"])
+    if not bool((s.vel0 != 0).any()):   # from zero velocities nothing moves before the live step
+        assert all(torch.equal(tr[k]["params"], s.case.flat) for k in range(kl + 1))
+
+
+@pytest.mark.parametrize("mut", sorted(LAUNCH_MUTATIONS))
+def test_planted_launch_errors_are_rejected(mut):
+    """Each planted error in the by-hand replay is rejected, by the comparator the GPU test uses
+    and against the expectation it uses, by every schedule listed for it (at least one)."""
+    must = [k for k in GPU.SCHEDULES if LAUNCH_MUTATIONS[mut](k)]
+    assert must, mut
+    for key in must:
+        s = GPU.schedule(key)
+        want = _sched_blocks(s.lay, s.run["params"], s.run["velocities"], s.run["loss_sum"])
+        bad = cx.block_mismatches(_launch_by_hand(s, mut), want)
+        assert bad, f"{mut} passes {s.tag}"
+        if mut == "dead_step_loss_dropped":
+            assert [line.split(":")[0] for line in bad] == ["loss"]
+
+
+def test_launch_proof_is_not_vacuous():
+    """cnn_launch_violations reports a dead batch whose targets sit within the clip, a still
+    batch under another step's mask, a second live step and a learning rate that leaves the
+    lattice."""
+    s = GPU.schedule((GPU.REF, 20, "mae_clip", 0.5, ("dead", "live", "dead"), True, False, False))
+    args = lambda steps, kinds=s.kinds, sgd=s.sgd: (s.case, s.vel0, steps, kinds, sgd, s.it0, cx.CLIP, GPU.LOSS0)  # noqa: E731
+    assert cx.cnn_launch_violations(*args(s.steps)) == []
+    x, y, mask = s.steps[2]
+    near = [s.steps[0], s.steps[1], (x, y + (s.run["trace"][2]["ref"]["pred"][:, :12] - y) * 0.75, mask)]
+    assert any("dead" in v for v in cx.cnn_launch_violations(*args(near)))
+    assert cx.cnn_launch_violations(*args(s.steps, ("dead", "live", "live"))) != []
+    assert cx.cnn_launch_violations(*args(s.steps, sgd=dict(s.sgd, lr=0.001))) != []
+    m = GPU.schedule((GPU.REF, 20, "mse", 0.5, ("still", "live"), True, False, False))
+    swapped = [(m.steps[0][0], m.steps[0][1], m.steps[1][2]), m.steps[1]]
+    bad = cx.cnn_launch_violations(m.case, m.vel0, swapped, m.kinds, m.sgd, m.it0, cx.CLIP, GPU.LOSS0)
+    assert any("still" in v for v in bad)

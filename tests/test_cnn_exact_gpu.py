@@ -44,7 +44,55 @@ IMAGE_O = (1, 12, 16)
 # problems in which the 16 or 17 residuals' dense-bias gradients cancelled to exactly 0
 # (tests/test_cnn_exact_cpu.py requires every gradient block of every problem to be nonzero).
 RESEED = {((48, 1, 112, 13, 1), 17, "mae_clip"): 1, ((44, 1, 100, 9, 1), 17, "mae_clip"): 1,
-          ((48, 1, 100, 13, 1), 16, "mse"): 1}
+          ((48, 1, 100, 13, 1), 16, "mse"): 1, ((48, 1, 97, 13, 1), 20, "mae_clip"): 1,
+          ((48, 1, 97, 13, 1), 20, "mse"): 1, ((48, 1, 109, 13, 1), 20, "mse"): 1,
+          ((48, 1, 109, 13, 1), 64, "mae_clip"): 1}
+
+# The small-batch kernel (csrc/cnn_small.hip): G = ceil(filters / 4) workgroups of 4 filters.
+# 97, 105 and 109 filters leave ONE live filter in the last workgroup; G = 25 / 27 / 28.
+SMALL_EDGE_LAYS = tuple((48, 1, F, 13, O) for F, O in ((97, 1), (100, 16), (105, 12), (109, 1), (112, 16)))
+SMALL_LAYS = (REF,) + SMALL_EDGE_LAYS
+BIG, TINY = (48, 1, 112, 13, 16), (48, 1, 97, 13, 1)   # with B = 64: hop 1's second trip; with B = 4: idle workers
+LOSS0 = 3.0                          # what loss_into holds before every small-kernel launch
+IT_STATE, DECAY_STATE = 16, 2.0 ** -4   # 1 + decay * it = 2: lr_t = lr / 2 exactly, and for no other counter
+STATE_KEYS = tuple((lay_t, B, loss, nes) for (lay_t, B) in ((REF, 20), (BIG, 64)) for loss in LOSSES
+                   for nes in (True, False))
+KERAS = {"lr": 0.001, "momentum": 0.99, "decay": 1e-6}   # the reference's optimizer (off the lattice)
+KERAS_IT = (0, 1, 10 ** 6)
+
+
+def small_branches(lay_t, B) -> dict:
+    """What the launcher and the kernel compute from (filters, outputs, B): the grid G, the
+    number of dense outputs, whether workgroups wk >= nout idle through hop 1 (nl = 0) and
+    whether workgroup 0's hop-1 loop over nl * G (output, share) pairs takes a second trip."""
+    G = (lay_t[2] + 3) // 4
+    nout = B * lay_t[4]
+    nl0 = (nout + G - 1) // G
+    return {"G": G, "nout": nout, "idle_workers": nout < G, "second_trip": nl0 * G > 1024,
+            "one_live_filter": lay_t[2] % 4 == 1}
+
+
+def _schedules():
+    """(layout, B, loss, dropout, kinds, nesterov, preset velocities, contiguous rows) of every
+    one-live-step launch below."""
+    out = []
+    d, s, l = "dead", "still", "live"
+    for lay_t, B in ((REF, 20), (BIG, 64), (TINY, 4)):
+        for kinds in ((l, d, d), (d, l, d), (d, d, l), (d, d, d, l)):
+            out.append((lay_t, B, "mae_clip", 0.5, kinds, True, False, False))
+        out.append((lay_t, B, "mse", 0.5, (s, s, l), True, False, False))
+        out.append((lay_t, B, "mse", 0.5, (s, l), True, False, False))
+        out.append((lay_t, B, "mae_clip", 0.5, (l, d, d), True, True, False))    # from the preset velocities
+    out.append((REF, 20, "mae_clip", 0.0, (d, l, d), True, False, False))        # no dropout, once per loss
+    out.append((REF, 20, "mse", 0.0, (s, l), True, False, False))
+    out.append((REF, 20, "mae_clip", 0.5, (l, d, d), False, False, False))       # plain momentum
+    out.append((REF, 20, "mae_clip", 0.5, (l, d, d), False, True, False))
+    out.append((REF, 20, "mae_clip", 0.5, (d, l, d), True, False, True))         # rows=None
+    out.append((REF, 20, "mse", 0.5, (s, s, l), True, False, True))
+    return tuple(out)
+
+
+SCHEDULES = _schedules()
 
 
 def _r16(n):
@@ -110,7 +158,7 @@ def all_problem_keys():
         keys += [(lay, B, loss, 0.5, "fused") for lay in EDGE_LAYS for B in EDGE_B]
         keys += [(REF, B, loss, 0.5, "fused") for B in STATE_B]
         keys += [(lay, B, loss, p, "gemm") for lay in GEMM_LAYS for p in (0.0, 0.5) for B in GEMM_B]
-        keys += [(REF, B, loss, p, "small") for p in (0.0, 0.5) for B in SMALL_B]
+        keys += [(lay, B, loss, p, "small") for lay in SMALL_LAYS for p in (0.0, 0.5) for B in SMALL_B]
     keys += [(lay, B, "mse", 0.0, "fused") for lay in EDGE_LAYS for B in EDGE_B]        # evaluation forward
     keys += [(REF, B, "mse", 0.0, "fused") for B in EVAL_B]
     keys += [((48, 1, 100, 13, O), 16, "mse", 0.0, "fused") for O in IMAGE_O]           # operand images
@@ -454,44 +502,306 @@ def test_cnn_gemm_path_step(lay_t, loss, dropout, B):
 
 
 # ---------------------------------------------------------------------- small-batch kernel
+class Schedule:
+    """One K-step launch in which exactly one step is live (wellflow/train/cnn_exact.py): the live
+    batch is the "small" problem of (layout, B, loss, dropout) with its targets redrawn under the
+    mask of ITS step, the others are distinct dead (clipped MAE) or still (MSE) batches. decay =
+    2^-4 and the counter preset to 16 - k_live, so lr_t is lr / 2 exactly at the live step only if
+    the kernel uses it0 + k. The batches are scattered through ``rows`` over a table of (K + 2) B
+    rows whose other rows hold other data, or laid out contiguously (``rows`` None)."""
+
+    def __init__(self, lay_t, B, loss, dropout, kinds, nesterov, preset, contiguous):
+        from wellflow.models.cnn import cnn_dropout_mask
+        from wellflow.train import cnn_exact as cx
+
+        self.key = (lay_t, B, loss, dropout, kinds, nesterov, preset, contiguous)
+        self.lay_t, self.B, self.loss, self.p, self.kinds, self.contiguous = lay_t, B, loss, dropout, kinds, contiguous
+        prob = problem(lay_t, B, loss, dropout, "small")
+        self.case, self.lay = case, lay = prob.case, prob.lay
+        self.K, self.k_live = len(kinds), kinds.index("live")
+        self.it0 = IT_STATE - self.k_live
+        self.sgd = {"lr": SGD["lr"], "momentum": SGD["momentum"], "nesterov": nesterov, "decay": DECAY_STATE}
+        seed = 7919 * lay.filters + 13 * B + self.K
+        self.vel0 = cx.lattice_velocities(lay, seed) if preset else torch.zeros(lay.numel, dtype=torch.float64)
+        self.steps = []
+        p, v = case.flat, self.vel0   # the state each step starts from: a dead batch's targets follow it
+        for k, kind in enumerate(kinds):
+            mask = cnn_dropout_mask(cx.seed32(SEED), STEP0 + k, B, lay.lout, lay.Fp) if dropout > 0 else None
+            if kind == "live":
+                x, y = case.x, cx.exact_cnn_targets(case, mask)
+            else:
+                x = cx.exact_cnn_case(lay, B, seed + 101 * (k + 1), loss, dropout).x
+                y = (cx.dead_targets(p, x, mask, case.keep_scale, lay, seed + k) if kind == "dead" else
+                     cx.still_targets(p, x, mask, case.keep_scale, lay))
+            self.steps.append((x, y, mask))
+            one = cx.cnn_launch_fp64(p, v, self.steps[-1:], case.grad_scale, loss, cx.CLIP, case.keep_scale, lay, self.sgd,
+                                     self.it0 + k)
+            p, v = one["params"], one["velocities"]
+        self.run = cx.cnn_launch_fp64(case.flat, self.vel0, self.steps, case.grad_scale, loss, cx.CLIP, case.keep_scale,
+                                      lay, self.sgd, self.it0)
+        self._violations = None
+
+    def violations(self):
+        from wellflow.train.cnn_exact import CLIP, cnn_launch_violations
+
+        if self._violations is None:
+            self._violations = cnn_launch_violations(self.case, self.vel0, self.steps, self.kinds, self.sgd, self.it0,
+                                                     CLIP, LOSS0)
+        return self._violations
+
+    def table(self, steps=None):
+        """(X [N][48], Y [N][outputs], rows or None), float64 / int64 on the host."""
+        from wellflow.train.cnn_exact import X_VALUES
+        from wellflow.train.exact import _pick
+
+        steps = self.steps if steps is None else steps
+        xs = torch.cat([s[0].reshape(self.B, -1) for s in steps])
+        ys = torch.cat([s[1] for s in steps])
+        if self.contiguous:
+            return xs, ys, None
+        g = torch.Generator().manual_seed(17 * self.B + self.K)
+        N = (self.K + 2) * self.B
+        X, Y = _pick(X_VALUES, (N, self.lay.input_len), g), _pick(X_VALUES, (N, self.lay.outputs), g)
+        rows = torch.randperm(N, generator=g)[: self.K * self.B]
+        X[rows], Y[rows] = xs, ys
+        return X, Y, rows
+
+    @property
+    def tag(self):
+        return (f"layout={self.lay_t} B={self.B} {self.loss} p={self.p} {'-'.join(self.kinds)} "
+                f"nesterov={self.sgd['nesterov']} it0={self.it0}")
+
+
+@functools.lru_cache(maxsize=None)
+def schedule(key) -> Schedule:
+    return Schedule(*key)
+
+
+def _sched_id(k):
+    return (f"F{k[0][2]}-O{k[0][4]}-B{k[1]}-{k[2]}-p{k[3]}-{'-'.join(k[4])}" + ("" if k[5] else "-plain")
+            + ("-preset" if k[6] else "") + ("-contiguous" if k[7] else ""))
+
+
+GRADS_FILL = 7.0   # the gradient bucket before a small-kernel launch (which must not write it)
+
+
+def small_engine(lay_t, B, loss, dropout, sgd):
+    """A fresh engine of capacity B with a FlatSGD of ``sgd`` (lr, momentum, nesterov, decay)."""
+    from wellflow.optim.flat import FlatSGD
+
+    eng = engine(lay_t, loss, dropout, B, cached=False)
+    opt = FlatSGD(eng.params, eng.grads, lr=sgd["lr"], momentum=sgd["momentum"], decay=sgd.get("decay", 0.0),
+                  nesterov=sgd["nesterov"], zero_grads=True, writeback=eng)
+    assert eng.small_steps_reason(B, opt) is None
+    return eng, opt
+
+
+def small_launch(eng, opt, flat, vel, it0, X, Y, rows, B, K, grad_scale):
+    """Parameters, velocities, both counters and the dropout step preset; then ONE launch of K
+    steps with loss_into starting from LOSS0. Returns the blocks to compare."""
+    eng.params.copy_(flat.float().to(DEV))
+    eng.sync_weights()
+    eng.rng.fill_(STEP0)
+    eng.grads.fill_(GRADS_FILL)
+    opt.vel.copy_(vel.float().to(DEV))
+    opt.step_dev.zero_()
+    opt.step_dev[0] = float(it0)
+    opt.iterations = it0
+    acc = torch.full((1,), LOSS0, device=DEV)
+    rows = None if rows is None else rows.to(DEV)
+    eng.fused_steps(X.float().to(DEV), Y.float().to(DEV), B, K, opt, grad_scale, rows=rows, loss_into=acc)
+    torch.cuda.synchronize()
+    eng.check_device_errors()
+    got = {"loss": acc.cpu(), "step": opt.step_dev[:1].cpu(), "ticket": opt.step_dev[1:].cpu(), "rng": eng.rng.cpu(),
+           "iterations": torch.tensor([opt.iterations]), "grads": eng.grads.cpu(), "WcA": eng.WcA.cpu()}
+    pc, vc = eng.lay.views(eng.params.cpu()), eng.lay.views(opt.vel.cpu())
+    for i, name in enumerate(("Wc", "Wd", "bd")):
+        got[f"{name} params"], got[f"{name} velocities"] = pc[i], vc[i]
+    return got
+
+
+def small_want(lay, pn, vn, loss_sum, it_end, K):
+    """The float64 parameters / velocities after the launch as the fp32 blocks small_launch
+    returns (all padding included: zero), the loss on top of LOSS0, both counters, the dropout
+    step, the refreshed conv image (a bf16 cast of the new conv block) and what the launch must
+    leave alone: the gradient bucket and the optimizer's ticket words."""
+    want_loss = LOSS0 + loss_sum
+    assert float(want_loss.float()) == float(want_loss)
+    want = {"loss": want_loss.reshape(1).float(), "step": torch.tensor([float(it_end)]), "ticket": torch.zeros(3),
+            "rng": torch.tensor([STEP0 + K], dtype=torch.int64), "iterations": torch.tensor([it_end]),
+            "grads": torch.full((lay.numel,), GRADS_FILL)}
+    pw, vw = lay.views(pn.float()), lay.views(vn.float())
+    for i, name in enumerate(("Wc", "Wd", "bd")):
+        want[f"{name} params"], want[f"{name} velocities"] = pw[i], vw[i]
+    want["WcA"] = pw[0].reshape(-1).to(torch.bfloat16)
+    return want
+
+
+def _small_one_step(lay_t, loss, dropout, B):
+    from wellflow.train.cnn_exact import keras_sgd_fp64
+
+    br = small_branches(lay_t, B)
+    assert br["G"] == {97: 25, 100: 25, 105: 27, 109: 28, 112: 28}[lay_t[2]]
+    assert br["one_live_filter"] == (lay_t[2] in (97, 105, 109))
+    assert br["idle_workers"] == (lay_t[4] == 1 and B <= 20)          # nout < G: workers with nl = 0
+    assert br["second_trip"] == (lay_t[4] == 16 and B == 64)          # nl * G > 1024
+    prob = problem(lay_t, B, loss, dropout, "small")
+    bad = prob.violations()
+    assert not bad, f"{prob.tag}: the problem is not exact, nothing launched: {bad}"
+    eng, opt = small_engine(lay_t, B, loss, dropout, SGD)
+    zero = torch.zeros(prob.lay.numel, dtype=torch.float64)
+    got = small_launch(eng, opt, prob.case.flat, zero, 0, prob.case.x.reshape(B, -1), prob.y, None, B, 1,
+                       prob.case.grad_scale)
+    pn, vn = keras_sgd_fp64(prob.case.flat, prob.ref["grads"], zero, SGD["lr"], SGD["momentum"], SGD["nesterov"])
+    check(got, small_want(prob.lay, pn, vn, prob.ref["loss_sum"], 1, 1), f"{prob.tag} {br}")
+
+
 @pytest.mark.parametrize("B", SMALL_B)
 @pytest.mark.parametrize("dropout", (0.0, 0.5))
 @pytest.mark.parametrize("loss", LOSSES)
 def test_cnn_small_kernel_one_step(loss, dropout, B):
     """fused_steps with K = 1 (cnn_small_kernel: forward, the one exchange, backward and the
     Keras SGD update in one launch) against float64 forward + backward + Keras update:
-    parameters and velocities after the launch, loss_into, the step counter and rng.
+    parameters and velocities of all three blocks with their padding, loss_into from a nonzero
+    start, both step counters, rng, the refreshed WcA; the gradient bucket and the ticket words
+    untouched.
 
-    K = 2 is not added: after one update the parameters are multiples of 2^-25 or finer, the
-    second step's dense outputs are sums of 1e11 and more quanta and its predictions no fp32
-    numbers; the proof rejects the second step of every problem here
-    (tests/test_cnn_exact_cpu.py::test_second_small_step_is_not_exact), so K > 1 stays with
+    Two LIVE steps cannot be exact: after one update the parameters are multiples of 2^-25 or
+    finer, the second step's dense outputs are sums of 1e11 and more quanta and its predictions
+    no fp32 numbers (tests/test_cnn_exact_cpu.py::test_second_small_step_is_not_exact). Steps
+    k >= 1 of a launch are pinned by test_cnn_small_kernel_one_live_step below (one live step
+    among batches whose gradient is exactly zero), several live steps on random data by
     test_small_gpu.py's "K fused = K single"."""
-    from wellflow.optim.flat import FlatSGD
-    from wellflow.train.cnn_exact import keras_sgd_fp64
+    _small_one_step(REF, loss, dropout, B)
 
-    prob = problem(REF, B, loss, dropout, "small")
-    eng = engine(REF, loss, dropout, B, cached=False)
-    opt = FlatSGD(eng.params, eng.grads, lr=SGD["lr"], momentum=SGD["momentum"], decay=0.0, nesterov=SGD["nesterov"],
-                  zero_grads=True, writeback=eng)
-    assert eng.small_steps_reason(B, opt) is None
-    load(eng, prob)
-    x, y = device_xy(prob)
-    acc = torch.full((1,), 3.0, device=DEV)
-    eng.fused_steps(x, y, B, 1, opt, prob.case.grad_scale, loss_into=acc)
-    torch.cuda.synchronize()
-    eng.check_device_errors()
-    pn, vn = keras_sgd_fp64(prob.case.flat, prob.ref["grads"], torch.zeros(prob.lay.numel, dtype=torch.float64),
-                            SGD["lr"], SGD["momentum"], SGD["nesterov"])
-    want_loss = 3.0 + prob.ref["loss_sum"]
-    assert float(want_loss.float()) == float(want_loss)
-    pc, vc = prob.lay.views(eng.params.cpu()), prob.lay.views(opt.vel.cpu())
-    pw, vw = prob.lay.views(pn.float()), prob.lay.views(vn.float())
-    got = {"loss": acc.cpu(), "step": opt.step_dev[:1].cpu(), "rng": eng.rng.cpu()}
-    want = {"loss": want_loss.reshape(1).float(), "step": torch.ones(1), "rng": torch.tensor([STEP0 + 1], dtype=torch.int64)}
-    for i, name in enumerate(("Wc", "Wd", "bd")):
-        got[f"{name} params"], want[f"{name} params"] = pc[i], pw[i]
-        got[f"{name} velocities"], want[f"{name} velocities"] = vc[i], vw[i]
-    check(got, want, prob.tag)
-    # the operand images were refreshed from the new parameters (plain bf16 casts of them)
-    assert torch.equal(eng.WcA.cpu(), pw[0].reshape(-1).to(torch.bfloat16))
+
+@pytest.mark.parametrize("B", SMALL_B)
+@pytest.mark.parametrize("dropout", (0.0, 0.5))
+@pytest.mark.parametrize("loss", LOSSES)
+@pytest.mark.parametrize("lay_t", SMALL_EDGE_LAYS, ids=lambda l: f"F{l[2]}-O{l[4]}")
+def test_cnn_small_kernel_one_step_edge_layouts(lay_t, loss, dropout, B):
+    """The same on the edges of what small_steps_reason and the launcher admit (97 .. 112 filters
+    x 1 .. 16 outputs): G = 25, 27 and 28 workgroups, ONE live filter in the last workgroup (97,
+    105, 109), workgroups without a hop-1 output (nout < G: one output, B = 4 and 20) and the
+    second trip of the hop-1 loop (nl * G > 1024: 16 outputs, B = 64); each case asserts the
+    branch it is listed for from B, O and G as the launcher computes them."""
+    _small_one_step(lay_t, loss, dropout, B)
+
+
+def state_sgd(nesterov, vel):
+    return {"lr": SGD["lr"], "momentum": SGD["momentum"], "nesterov": nesterov, "decay": DECAY_STATE,
+            "iteration": IT_STATE, "velocities": vel}
+
+
+def state_velocities(prob):
+    from wellflow.train.cnn_exact import lattice_velocities
+
+    return lattice_velocities(prob.lay, 31 * prob.lay.filters + prob.B)
+
+
+@pytest.mark.parametrize("lay_t,B,loss,nesterov", STATE_KEYS, ids=lambda v: f"F{v[2]}-O{v[4]}" if isinstance(v, tuple) else str(v))
+def test_cnn_small_kernel_step_from_preset_state(lay_t, B, loss, nesterov):
+    """One step from a state that is not zero, bit for bit: velocities preset on the lattice
+    (multiples of 1/8, zero on the padding), Nesterov and plain momentum, the device counter
+    preset to 16 with decay 2^-4 (lr_t = lr / 2 exactly; any other counter gives another lr_t)."""
+    from wellflow.train.cnn_exact import CLIP, cnn_exactness_violations, keras_sgd_fp64
+
+    prob = problem(lay_t, B, loss, 0.5, "small")
+    vel = state_velocities(prob)
+    sgd = state_sgd(nesterov, vel)
+    bad = cnn_exactness_violations(prob.case, prob.y, prob.mask, "small", CLIP, sgd)
+    assert not bad, f"{prob.tag}: not exact from the preset state, nothing launched: {bad}"
+    eng, opt = small_engine(lay_t, B, loss, 0.5, sgd)
+    got = small_launch(eng, opt, prob.case.flat, vel, IT_STATE, prob.case.x.reshape(B, -1), prob.y, None, B, 1,
+                       prob.case.grad_scale)
+    pn, vn = keras_sgd_fp64(prob.case.flat, prob.ref["grads"], vel, sgd["lr"], sgd["momentum"], nesterov, DECAY_STATE,
+                            IT_STATE)
+    assert not torch.equal(vn, keras_sgd_fp64(prob.case.flat, prob.ref["grads"], vel * 0, sgd["lr"], sgd["momentum"],
+                                              nesterov, DECAY_STATE, IT_STATE)[1])
+    check(got, small_want(prob.lay, pn, vn, prob.ref["loss_sum"], IT_STATE + 1, 1), f"{prob.tag} nesterov={nesterov}")
+
+
+@pytest.mark.parametrize("it", KERAS_IT)
+@pytest.mark.parametrize("nesterov", (True, False))
+@pytest.mark.parametrize("lay_t,B", ((REF, 20), (BIG, 64)), ids=("F100-O12-B20", "F112-O16-B64"))
+def test_cnn_small_kernel_keras_decay_within_bound(lay_t, B, nesterov, it):
+    """The reference's optimizer (lr 0.001, momentum 0.99, decay 1e-6) with the counter at 0, 1
+    and 10^6, from lattice velocities: the gradient is exact, only the update rounds, so every
+    parameter and velocity lies within train/optim_ref.py sgd_tol of sgd_fp64 (the bound derived
+    for this very formula: the kernel's ``sgd`` lambda); the padding, where the bound is 0, is
+    unchanged. Measured worst error / bound on an MI355X: see COVERAGE.md row K8."""
+    from wellflow.train import optim_ref as R
+
+    prob = problem(lay_t, B, "mae_clip", 0.5, "small")
+    assert not prob.violations()
+    vel = state_velocities(prob)
+    lr, mu, decay = R.f32(KERAS["lr"]), R.f32(KERAS["momentum"]), R.f32(KERAS["decay"])
+    eng, opt = small_engine(lay_t, B, "mae_clip", 0.5, dict(KERAS, nesterov=nesterov))
+    got = small_launch(eng, opt, prob.case.flat, vel, it, prob.case.x.reshape(B, -1), prob.y, None, B, 1,
+                       prob.case.grad_scale)
+    g = prob.ref["grads"]
+    pn, vn = R.sgd_fp64(prob.case.flat, g, vel, it, lr, mu, nesterov, decay)
+    tol_p, tol_v = R.sgd_tol(pn, g, vel, vn, it, lr, mu, nesterov, decay)
+    gp = torch.cat([got[f"{n} params"].reshape(-1) for n in ("Wc", "Wd", "bd")]).double()
+    gv = torch.cat([got[f"{n} velocities"].reshape(-1) for n in ("Wc", "Wd", "bd")]).double()
+    worst = {}
+    for name, have, ref, tol in (("p", gp, pn, tol_p), ("vel", gv, vn, tol_v)):
+        err = (have - ref).abs()
+        live = tol > 0
+        worst[name] = float((err[live] / tol[live]).max())
+        assert bool((err[~live] == 0).all()), f"{name}: an element with a zero bound changed"
+    print(f"[cnn_small sgd] F={lay_t[2]} O={lay_t[4]} B={B} nesterov={nesterov} it={it} worst error / bound: "
+          f"p {worst['p']:.3f} vel {worst['vel']:.3f}")
+    assert worst["p"] <= 1.0 and worst["vel"] <= 1.0, worst
+    rest = small_want(prob.lay, pn, vn, prob.ref["loss_sum"], it + 1, 1)
+    rest = {k: rest[k] for k in ("loss", "step", "ticket", "rng", "iterations", "grads")}
+    rest["WcA"] = got["Wc params"].reshape(-1).to(torch.bfloat16)   # the image of what the kernel wrote
+    check(got, rest, f"{prob.tag} keras it={it}")
+
+
+@pytest.mark.parametrize("ids", ("inside", "clamped"))
+@pytest.mark.parametrize("loss", LOSSES)
+@pytest.mark.parametrize("lay_t,B", ((REF, 20), (BIG, 64)), ids=("F100-O12-B20", "F112-O16-B64"))
+def test_cnn_small_kernel_rows(lay_t, B, loss, ids):
+    """The batch read through ``rows`` from a table of 3 B rows whose other rows hold other
+    data, the batch's windows at scattered positions that include the first and the last row.
+    "clamped": the ids of those two are -3 and N + 5; the kernel clamps every id into [0, N), so
+    the launch equals the one with ids 0 and N - 1."""
+    from wellflow.train.cnn_exact import X_VALUES, keras_sgd_fp64
+    from wellflow.train.exact import _pick
+
+    prob = problem(lay_t, B, loss, 0.5, "small")
+    assert not prob.violations()
+    N = 3 * B
+    g = torch.Generator().manual_seed(23)
+    X, Y = _pick(X_VALUES, (N, prob.lay.input_len), g), _pick(X_VALUES, (N, prob.lay.outputs), g)
+    rows = torch.randperm(N - 2, generator=g)[:B] + 1
+    rows[3], rows[B - 1] = 0, N - 1
+    X[rows], Y[rows] = prob.case.x.reshape(B, -1), prob.y
+    assert not torch.equal(X[:B], prob.case.x.reshape(B, -1)) and not torch.equal(rows, rows.sort().values)
+    if ids == "clamped":
+        rows[3], rows[B - 1] = -3, N + 5
+    eng, opt = small_engine(lay_t, B, loss, 0.5, SGD)
+    zero = torch.zeros(prob.lay.numel, dtype=torch.float64)
+    got = small_launch(eng, opt, prob.case.flat, zero, 0, X, Y, rows, B, 1, prob.case.grad_scale)
+    pn, vn = keras_sgd_fp64(prob.case.flat, prob.ref["grads"], zero, SGD["lr"], SGD["momentum"], SGD["nesterov"])
+    check(got, small_want(prob.lay, pn, vn, prob.ref["loss_sum"], 1, 1), f"{prob.tag} rows {ids}")
+
+
+@pytest.mark.parametrize("key", SCHEDULES, ids=_sched_id)
+def test_cnn_small_kernel_one_live_step(key):
+    """K = 2 .. 4 steps in ONE launch, exactly one of them live (class Schedule), against the
+    float64 replay of the launch, bit for bit: this pins, for steps k >= 1, the dropout step
+    rng0 + k (a still step under another mask is live; the live step's targets are drawn under its
+    own), it0 + k (lr_t is lr / 2 only at the live step's counter), ``rows[k B + w]`` and the
+    two-ahead prefetch (distinct batches), both parities of the exchange buffers twice (K = 4), and
+    the momentum carried in LDS: after [live, dead, dead] the velocity has decayed twice and the
+    parameters have moved each time. Each dead step adds exactly B * outputs * CLIP to the loss."""
+    s = schedule(key)
+    bad = s.violations()
+    assert not bad, f"{s.tag}: the launch is not exact, nothing launched: {bad}"
+    eng, opt = small_engine(s.lay_t, s.B, s.loss, s.p, s.sgd)
+    X, Y, rows = s.table()
+    got = small_launch(eng, opt, s.case.flat, s.vel0, s.it0, X, Y, rows, s.B, s.K, s.case.grad_scale)
+    run = s.run
+    check(got, small_want(s.lay, run["params"], run["velocities"], run["loss_sum"], s.it0 + s.K, s.K), s.tag)

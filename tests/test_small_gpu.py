@@ -167,11 +167,11 @@ def test_small_spin_bound_fails_loudly():
 
 
 # ---------------------------------------------------------------------------- CNN (B = 20)
-def _cnn_setup(B=20, N=None, seed=4, loss="mae_clip", dropout=0.5):
+def _cnn_setup(B=20, N=None, seed=4, loss="mae_clip", dropout=0.5, layout=None):
     from wellflow.models.cnn import CNN1DRegressor, CnnLayout, NativeCNN
     from wellflow.optim.flat import FlatSGD
 
-    lay = CnnLayout()
+    lay = CnnLayout() if layout is None else CnnLayout(*layout)
     torch.manual_seed(seed)
     ref = CNN1DRegressor(lay.input_len, lay.in_ch, lay.filters, lay.kernel, lay.outputs).init_keras(seed)
     with torch.no_grad():
@@ -190,16 +190,15 @@ def _cnn_setup(B=20, N=None, seed=4, loss="mae_clip", dropout=0.5):
     return eng, opt, ref, X, Y, lay
 
 
-def test_cnn_small_k_fused_equals_k_single():
-    B, K = 20, 8
+def _cnn_fused_vs_single(B, K, splits, layout=None):
     out = []
-    for split in ([8], [1] * 8, [3, 5]):
-        eng, opt, _, X, Y, _ = _cnn_setup(B=B)
+    for split in splits:
+        eng, opt, _, X, Y, lay = _cnn_setup(B=B, layout=layout)
         rows = torch.randperm(X.shape[0], generator=torch.Generator().manual_seed(2))[: K * B].to(DEV)
         acc = torch.zeros(1, device=DEV)
         s = 0
         for k in split:
-            eng.fused_steps(X, Y, B, k, opt, 1.0 / (B * 12), rows=rows[s * B : (s + k) * B], loss_into=acc)
+            eng.fused_steps(X, Y, B, k, opt, 1.0 / (B * lay.outputs), rows=rows[s * B : (s + k) * B], loss_into=acc)
             s += k
         torch.cuda.synchronize()
         eng.check_device_errors()
@@ -208,6 +207,20 @@ def test_cnn_small_k_fused_equals_k_single():
     for other in out[1:]:
         for a, b in zip(out[0], other):
             assert torch.equal(a, b)
+    assert bool(torch.isfinite(out[0][0]).all()) and float(out[0][4]) > 0
+
+
+def test_cnn_small_k_fused_equals_k_single():
+    _cnn_fused_vs_single(20, 8, ([8], [1] * 8, [3, 5]))
+
+
+@pytest.mark.parametrize("layout,B", [((48, 1, 112, 13, 16), 64), ((48, 1, 97, 13, 1), 4)], ids=["F112-O16-B64", "F97-O1-B4"])
+def test_cnn_small_k_fused_equals_k_single_edge_layouts(layout, B):
+    """The same on the edges of what the launcher admits: 28 workgroups and a second trip of the
+    hop-1 loop (1024 outputs); 25 workgroups of which 21 own no hop-1 output and the last owns one
+    live filter. Five live steps on random data, as [5], [1] x 5 and [2, 3]; the single launch on
+    these layouts is anchored to float64 by tests/test_cnn_exact_gpu.py."""
+    _cnn_fused_vs_single(B, 5, ([5], [1] * 5, [2, 3]), layout)
 
 
 @pytest.mark.parametrize("loss,dropout", [("mae_clip", 0.5), ("mse", 0.0)])
