@@ -81,30 +81,11 @@ def rank_shard(X, Y, chunk: int, rank: int, world: int, unit: int = 1):
 
 
 def _train_chunk_streamed(trainer, streamer, b):
-    """Consume the streamer's oldest queued chunk (this rank's batches of b rows)."""
-    from .step import StepRunner
-
-    ctx, eng = trainer.ctx, trainer.eng
-    run = trainer._runners.get("stream")
-    if run is None or run.grad_scale != 1.0 / (b * ctx.world_size * trainer.n_out):
-        run = StepRunner(eng, trainer.opt, ctx, 1.0 / (b * ctx.world_size * trainer.n_out),
-                         lambda k: tuple(streamer.slots[k][:2]))
-        trainer._runners = {"stream": run}
+    """Consume the streamer's oldest queued chunk (this rank's batches of b rows): one step per
+    ring slot, through the slot's own captured graph -> Trainer.run_pass's result."""
+    run = trainer._runner("stream", b, lambda k: tuple(streamer.slots[k][:2]))
     run.take_loss()
-    from .trainer import StepClock
-
-    clock = StepClock(eng.device)
-    done = 0
-    for slot in streamer:
-        clock.first()
-        run.run(slot)
-        done += 1
-        if trainer._after_step():
-            break
-    dt, trainer.last_host_dt = clock.stop()
-    (tot,) = ctx.sum_scalars(run.take_loss())
-    rows = done * b * ctx.world_size
-    return tot / max(rows * trainer.n_out, 1), rows, dt
+    return trainer.run_pass(run, ((slot, 1) for slot in streamer), lambda slot, _: run.run(slot), b)
 
 
 class _ChunkStage:
@@ -118,7 +99,6 @@ class _ChunkStage:
         self.n = [0, 0]
         self.events = [None, None]
         self.stream = torch.cuda.Stream(dev)
-        self._order = {}
 
     def copy(self, i: int, off: int, rows: int) -> None:
         xb, yb = self.bufs[i % 2]
@@ -135,13 +115,6 @@ class _ChunkStage:
     def take(self, i: int):
         torch.cuda.current_stream(self.dev).wait_event(self.events[i % 2])
         return self.bufs[i % 2]
-
-    def order(self, rows: int) -> torch.Tensor:
-        """A length-``rows`` stand-in for train_steps' order (sliced steps read none of it)."""
-        o = self._order.get(rows)
-        if o is None:
-            o = self._order[rows] = torch.empty(rows, dtype=torch.long, device=self.dev)
-        return o
 
 
 def fit_online(trainer, train, val):
@@ -179,7 +152,7 @@ def fit_online(trainer, train, val):
     # small batches (the job default: 256 rows) on one GPU: a chunk is ONE host -> HBM copy into
     # a device buffer (two, alternating: the next chunk copies while this one is validated) and
     # its mini-batches, in the same arrival order, run as K-step persistent launches
-    # (NativeMLP.fused_steps through Trainer.train_steps(sliced=True)); the per-batch ring +
+    # (NativeMLP.fused_steps through Trainer.train_steps on the rows in place); the per-batch ring +
     # one-step graphs held the default job at 5.8 M rows/s
     staged = None
     if streamed and plans:
@@ -203,8 +176,8 @@ def fit_online(trainer, train, val):
             if fed < i:
                 staged.copy(i, off, per_rank)
                 fed = i
-            Xd, Yd = staged.take(i)
-            tr_loss, rows, dt = trainer.train_steps(Xd, Yd, staged.order(per_rank), b_full, sliced=True)
+            # (rows: the buffers hold the largest chunk, this one fills their first per_rank rows)
+            result = trainer.train_steps(*staged.take(i), b_full, rows=per_rank)
             if i + 1 < len(plans) and on_ring[i + 1]:
                 staged.copy(i + 1, plans[i + 1][1], plans[i + 1][3])
                 fed = i + 1
@@ -212,7 +185,7 @@ def fit_online(trainer, train, val):
             if fed < i:
                 feed(i)
                 fed = i
-            tr_loss, rows, dt = _train_chunk_streamed(trainer, streamer, b_full)
+            result = _train_chunk_streamed(trainer, streamer, b_full)
             if i + 1 < len(plans) and on_ring[i + 1]:
                 # the next chunk's first batches copy host -> HBM while this one is validated:
                 # it then starts on batches already on the device (round-3 VERDICT missing #5)
@@ -224,31 +197,11 @@ def fit_online(trainer, train, val):
             b = max(1, min(b_full, per_rank))
             Xd, Yd = _to_dev(Xr, eng.device), _to_dev(Yr, eng.device)
             order = torch.arange(0, per_rank, device=eng.device)
-            tr_loss, rows, dt = trainer.train_steps(Xd, Yd, order, b)
-        eng.check_device_errors()
-        v_loss, v_mse = trainer.evaluate(*val)
+            result = trainer.train_steps(Xd, Yd, b, order)
         k += 1
         trainer.extra_state["chunks_done"] = k
-        trainer.epoch += 1
-        h = trainer.history
-        h.loss.append(tr_loss)
-        h.val_loss.append(v_loss)
-        h.val_mse.append(v_mse)
-        h.epoch_time.append(time.perf_counter() - t0)
-        hd = getattr(trainer, "last_host_dt", dt)
-        h.rows_per_s.append(rows / hd if hd > 0 else 0.0)
-        h.rows_per_s_device.append(rows / dt if dt > 0 else 0.0)
-        if cfg.verbose >= 2:
-            trainer.log(f"Chunk {k} (pass {p + 1}/{passes}) - {n_rows} rows - loss: {tr_loss:.6f}"
-                        f" - val_loss: {v_loss:.6f} - rows/s: {h.rows_per_s[-1]:.0f}", flush=True)
-        improved = v_loss < trainer.stopper.best
-        trainer.stopper.update(v_loss)
-        if improved and trainer.on_best is not None:
-            ctx.barrier()
-            if ctx.is_main:
-                trainer.on_best(trainer)
-            ctx.barrier()
-        trainer.save_state()
-        if trainer.stopper.stopped or (cfg.max_steps and trainer.global_step >= cfg.max_steps):
-            return trainer.history
+        if trainer.close_round(result, val, t0, lambda h: (
+                f"Chunk {k} (pass {p + 1}/{passes}) - {n_rows} rows - loss: {h.loss[-1]:.6f}"
+                f" - val_loss: {h.val_loss[-1]:.6f} - rows/s: {h.rows_per_s[-1]:.0f}")):
+            break
     return trainer.history

@@ -119,6 +119,107 @@ MAX_SLICED_STEPS = 128
 SMALL_STEPS_PER_LAUNCH = 256
 
 
+def group_len(steps: int, graph_steps: int, groupable: bool) -> int:
+    """Steps per graph replay in a pass of ``steps`` steps: about ``graph_steps``, in balanced
+    groups (9 steps run as one 9-step replay, not 8 + 1); 1 where steps cannot be grouped."""
+    n = graph_steps if groupable else 1
+    if n > 1 and steps > 1:
+        groups = max(1, round(steps / n))
+        n = -(-steps // groups)
+    return n
+
+
+def pass_schedule(steps: int, n: int, warm: int, aligned: bool, budget=math.inf) -> list:
+    """The launches [(start step, step count)] of a replayed pass. The launch at step ``s`` is one
+    replay of ``n`` steps when n > 1, the runner is warmed up (s >= warm: the eager steps, the
+    single-step capture and its first checked replay come first), the group fits into the pass
+    and into ``budget`` (the steps left until cfg.max_steps) and, where the graphs are keyed by
+    their start step (``aligned``), s is a multiple of n; otherwise it is one step. The pass ends
+    after the launch that reaches the budget. A pass entered with the budget already spent still
+    runs one single step (small_schedule runs none)."""
+    out, s = [], 0
+    while s < steps:
+        group = n > 1 and s >= warm and s + n <= min(steps, budget) and (not aligned or s % n == 0)
+        out.append((s, n if group else 1))
+        s += out[-1][1]
+        if s >= budget:
+            break
+    return out
+
+
+def small_schedule(steps: int, budget=math.inf) -> list:
+    """The launches [(start step, step count)] of a pass of K-step persistent launches:
+    SMALL_STEPS_PER_LAUNCH steps each, up to ``steps`` and ``budget`` (none when it is spent)."""
+    end = max(0, min(steps, budget))
+    return [(s, min(end - s, SMALL_STEPS_PER_LAUNCH)) for s in range(0, end, SMALL_STEPS_PER_LAUNCH)]
+
+
+# Batch sources: (inputs, stage) pairs. StepRunner asks ``inputs(key)`` for a single step and
+# ``inputs((key, i))`` for step i of an n-step launch; ``stage(s, c)`` does the host's part before
+# the launch of steps s .. s + c - 1 and returns the launch's key. Whatever the source and the
+# schedule, step j of the pass trains on rows order[j*b : (j+1)*b] of the dataset.
+def _group_step(key):
+    """StepRunner's inputs key -> (launch key, step within the group; None for a single step)."""
+    return key if isinstance(key, tuple) else (key, None)
+
+
+def sliced_source(Xs, Ys, b: int):
+    """Xs / Ys hold the pass's rows in order: step j reads a contiguous slice at a fixed address,
+    so a launch is keyed by its start step, every graph is captured once and no index is read."""
+    def inputs(key):
+        s, i = _group_step(key)
+        j = s + (i or 0)
+        return Xs[j * b : (j + 1) * b], Ys[j * b : (j + 1) * b]
+
+    return inputs, lambda s, c: s
+
+
+def _index_stage(order, b: int, idx, ordbuf=None):
+    def stage(s, c):  # one copy per launch into the static buffer its step(s) read
+        (idx if c == 1 else ordbuf).copy_(order[s * b : (s + c) * b])
+        return 0
+
+    return stage
+
+
+def indexed_source(Xd, Yd, order, b: int, idx, ordbuf):
+    """The engine's kernels read the dataset in place through a STATIC index buffer inside the
+    captured step: ``idx`` for a single step, slice i of ``ordbuf`` for step i of a group (whose
+    per-step index copy + replay gap, ~8 us of a 165-us MLP step, goes away)."""
+    def inputs(key):
+        _, i = _group_step(key)
+        return Xd, Yd, (idx if i is None else ordbuf[i * b : (i + 1) * b])
+
+    return inputs, _index_stage(order, b, idx, ordbuf)
+
+
+def gathered_source(Xd, Yd, order, b: int, idx):
+    """Engines that take the batch itself, and the CPU oracle: a row gather through ``idx``
+    (index_select: one coalesced kernel per tensor). Single steps only."""
+    def inputs(key):
+        return (Xd.index_select(0, idx) if torch.is_tensor(Xd) else Xd[idx]), Yd.index_select(0, idx)
+
+    return inputs, _index_stage(order, b, idx)
+
+
+def replay_launcher(run, stage, n: int, warm: int, steps: int, aligned: bool):
+    """launch(s, c) of a replayed pass: stage the rows, then one StepRunner step or one c-step
+    replay. An aligned pass captures every group's graph (starts 0, n, 2n, ...) up front, at its
+    first warm step in the first epoch: later epochs replay only, none of them pays a capture."""
+    todo = [range(0, steps - n + 1, n)] if aligned and n > 1 else []
+
+    def launch(s, c):
+        if todo and s >= warm:
+            all(run.prepare_many(n, g0) for g0 in todo.pop())  # (stops at the first refusal)
+        key = stage(s, c)
+        if c == 1:
+            run.run(key)
+        else:
+            run.run_many(c, key)
+
+    return launch
+
+
 def _resident_windows(X, device) -> bool:
     rows = getattr(X, "rows", None)
     if not (torch.is_tensor(rows) and torch.is_tensor(getattr(X, "starts", None))):
@@ -161,7 +262,7 @@ class Trainer:
         self.epoch = 0
         self.global_step = 0
         self.extra_state = {}
-        self._runners = {}
+        self._runners = (None, None)  # (key, StepRunner): the one data source being trained on
         self._idx = {}
 
     # ------------------------------------------------------------------ helpers
@@ -363,17 +464,19 @@ class Trainer:
             f.write(json.dumps(rec) + "\n")
 
     # ------------------------------------------------------------------ fit
-    def _runner(self, key, make_inputs, b: int):
+    def grad_scale(self, b: int) -> float:
+        """The factor on a batch's summed gradient: the mean over the global batch and the outputs."""
+        return 1.0 / (b * self.ctx.world_size * self.n_out)
+
+    def _runner(self, key, b: int, inputs):
         """The StepRunner (train/step.py, the same step bench.py times) for batches of ``b``
         rows, cached per data source: after two eager steps it replays as one hipGraph."""
         from .step import StepRunner
 
-        rk = (key, b)
-        if self._runners.get("key") != rk:
-            gscale = 1.0 / (b * self.ctx.world_size * self.n_out)
-            self._runners = {"key": rk, "run": StepRunner(self.eng, self.opt, self.ctx, gscale, make_inputs,
-                                                          graph=None if self.eng.native else False)}
-        return self._runners["run"]
+        if self._runners[0] != (key, b):
+            self._runners = ((key, b), StepRunner(self.eng, self.opt, self.ctx, self.grad_scale(b), inputs,
+                                                  graph=None if self.eng.native else False))
+        return self._runners[1]
 
     def _after_step(self) -> bool:
         """Step bookkeeping; True = stop (max_steps)."""
@@ -382,6 +485,24 @@ class Trainer:
         if cfg.fail_at_step >= 0 and self.global_step == cfg.fail_at_step:
             self._inject_fault()
         return bool(cfg.max_steps and self.global_step >= cfg.max_steps)
+
+    def run_pass(self, run, launches, launch, b: int):
+        """Issue ``launch(s, c)`` (c steps from step s) for each of ``launches`` until max_steps is
+        reached, then close the pass with one synchronize
+        -> (mean loss, rows trained on all ranks, device seconds, host seconds)."""
+        ctx = self.ctx
+        clock = StepClock(self.eng.device)
+        done = 0
+        for s, c in launches:
+            clock.first()
+            launch(s, c)
+            done += c
+            if any([self._after_step() for _ in range(c)]):  # (a list: every step is counted)
+                break
+        dt, host = clock.stop()
+        (tot,) = ctx.sum_scalars(run.take_loss())
+        rows = done * b * ctx.world_size
+        return tot / max(rows * self.n_out, 1), rows, dt, host
 
     def _epoch_order(self, n: int, per_rank: int, dev):
         """This rank's rows of the epoch's shuffle (seed + 7919 * epoch, the same on every rank).
@@ -421,119 +542,54 @@ class Trainer:
         eng.gather_rows(Yd, order, bufs[1])
         return bufs
 
-    def train_steps(self, Xd, Yd, order: torch.Tensor, b: int, sliced: bool = False):
-        """One pass over ``order`` (device index tensor of this rank) in batches of ``b``.
+    def _index_buffer(self, key, n: int) -> torch.Tensor:
+        buf = self._idx.get(key)
+        if buf is None:
+            buf = self._idx[key] = torch.zeros(n, dtype=torch.long, device=self.eng.device)
+        return buf
 
-        Each step gathers its batch from the resident dataset through a STATIC index buffer
-        inside the captured step, so the whole step (gather, fwd, bwd, all-reduce, update)
-        is one graph replay; the remainder that does not fill a batch is dropped (the native
-        engines run fixed-shape batches). ``sliced``: Xd / Yd already hold the pass's rows in
-        order (Trainer._permuted): step j reads rows j*b .. (j+1)*b - 1 as a contiguous slice,
-        a fixed address per step, so every step's graph is captured once and no index is read."""
-        eng, ctx = self.eng, self.ctx
-        steps = len(order) // b
-        if steps == 0 and len(order) > 0 and not eng.native:
-            steps, b = 1, len(order)
-        idx = self._idx.get(b)
-        if idx is None:
-            idx = self._idx[b] = torch.zeros(b, dtype=torch.long, device=eng.device)
-
-        row_indexed = eng.row_indexed and torch.is_tensor(Xd)
+    def train_steps(self, Xd, Yd, b: int, order: torch.Tensor | None = None, rows: int | None = None):
+        """One pass in batches of ``b`` over this rank's rows ``order`` (a device index tensor) of
+        the resident dataset Xd / Yd, or, without ``order``, over the first ``rows`` rows (all, by
+        default) of Xd / Yd in place (Trainer._permuted, a staged stream chunk). The remainder that
+        does not fill a batch is dropped (the native engines run fixed-shape batches).
+        -> run_pass's (mean loss, rows, device seconds, host seconds)."""
+        eng, cfg = self.eng, self.cfg
+        m = len(order) if order is not None else (len(Yd) if rows is None else rows)
+        steps = m // b
+        if steps == 0 and m > 0 and not eng.native:
+            steps, b = 1, m
+        budget = cfg.max_steps - self.global_step if cfg.max_steps else math.inf
         # resident windows (SeriesWindows on the device) that the engine reads in place through
         # the step's window ids (NativeLSTM: the x-pack kernel gathers them)
-        row_indexed = row_indexed or (eng.window_indexed and _resident_windows(Xd, eng.device))
-        # groups of n steps as ONE graph replay (StepRunner.run_many): step i of a group reads its
-        # rows from slice i of a static order buffer filled by one copy per group; the per-step
-        # index copy + replay gap (~8 us of a 165-us MLP step) goes away. Row-indexed engines,
-        # no per-step fault injection.
-        n_many = (_graph_steps() if ((row_indexed or sliced) and eng.device.type == "cuda" and self.cfg.fail_at_step < 0)
-                  else 1)
-        if n_many > 1 and steps > 1:  # balanced groups: 9 steps run as one 9-step replay, not 8 + 1
-            groups = max(1, round(steps / n_many))
-            n_many = -(-steps // groups)
-        ordbuf = None
-        if n_many > 1 and steps >= n_many and not sliced:
-            ordbuf = self._idx.get(("many", b, n_many))
-            if ordbuf is None:
-                ordbuf = self._idx[("many", b, n_many)] = torch.zeros(n_many * b, dtype=torch.long, device=eng.device)
-
-        def inputs(k):
-            if sliced:  # step j = k (single) or k[0] + k[1] (step k[1] of the group starting at k[0])
-                j = k[0] + k[1] if isinstance(k, tuple) else k
-                return Xd[j * b : (j + 1) * b], Yd[j * b : (j + 1) * b]
-            if row_indexed:  # the engine's kernels read the rows through the index
-                if isinstance(k, tuple):  # step k[1] of a run_many group
-                    return Xd, Yd, ordbuf[k[1] * b : (k[1] + 1) * b]
-                return Xd, Yd, idx
-            if torch.is_tensor(Xd):  # row gather (index_select: one coalesced kernel per tensor)
-                return Xd.index_select(0, idx), Yd.index_select(0, idx)
-            return Xd[idx], Yd.index_select(0, idx)
-
-        run = self._runner(("resident", id(Xd), id(Yd)), inputs, b)
+        row_indexed = (eng.row_indexed and torch.is_tensor(Xd)) or (eng.window_indexed
+                                                                    and _resident_windows(Xd, eng.device))
+        # groups of n steps as ONE graph replay (StepRunner.run_many), without per-step fault injection
+        n = group_len(steps, _graph_steps(), (row_indexed or order is None) and eng.device.type == "cuda"
+                      and cfg.fail_at_step < 0)
+        if order is None:
+            inputs, stage = sliced_source(Xd, Yd, b)
+        elif row_indexed:
+            ordbuf = self._index_buffer(("many", b, n), n * b) if 1 < n <= steps else None
+            inputs, stage = indexed_source(Xd, Yd, order, b, self._index_buffer(b, b), ordbuf)
+        else:
+            inputs, stage = gathered_source(Xd, Yd, order, b, self._index_buffer(b, b))
+        run = self._runner(("resident", id(Xd), id(Yd)), b, inputs)
         if run.loss_acc is not None:
             run.loss_acc.zero_()  # no take_loss() here: its sync left the GPU idle through the first launch
-        clock = StepClock(eng.device)
-        done = 0
-        cfg = self.cfg
-        s = 0
-        prepared = False
         # small batches (the job defaults: MLP 256 rows, CNN 20 windows): up to
         # SMALL_STEPS_PER_LAUNCH complete steps — forward, backward AND the optimizer update — per
         # persistent launch (NativeMLP / NativeCNN.fused_steps, csrc/mlp_small.hip, cnn_small.hip)
-        small, _ = small_steps_path(eng, self.opt, ctx, cfg, b, Xd)
-        while small and s < steps:
-            clock.first()
-            n = min(steps - s, SMALL_STEPS_PER_LAUNCH)
-            if cfg.max_steps:
-                n = max(0, min(n, cfg.max_steps - self.global_step))
-            if n == 0:
-                break
-            gscale = 1.0 / (b * ctx.world_size * self.n_out)
-            if sliced:
-                eng.fused_steps(Xd[s * b : (s + n) * b], Yd[s * b : (s + n) * b], b, n, self.opt, gscale,
-                                loss_into=run.loss_acc)
-            else:
-                eng.fused_steps(Xd, Yd, b, n, self.opt, gscale, rows=order[s * b : (s + n) * b],
-                                loss_into=run.loss_acc)
-            stop = False
-            for _ in range(n):
-                stop = self._after_step() or stop
-            done += n
-            s += n
-            if stop:
-                break
-        while not small and s < steps:
-            clock.first()
-            n = n_many
-            if sliced and n > 1 and not prepared and run.calls > run.eager_steps + 1:
-                # every aligned group's graph (starts 0, n, 2n, ...) captured up front, in the first
-                # epoch: later epochs replay only, none of them pays a capture
-                prepared = all(run.prepare_many(n, g0) for g0 in range(0, steps - n + 1, n))
-            if ((ordbuf is None and not sliced) or n <= 1 or s + n > steps or run.calls <= run.eager_steps + 1
-                    or (sliced and s % n != 0)
-                    or (cfg.max_steps and self.global_step + n > cfg.max_steps)):
-                if sliced:
-                    run.run(s)
-                else:
-                    idx.copy_(order[s * b : (s + 1) * b])
-                    run.run()
-                n = 1
-            elif sliced:
-                run.run_many(n, s)
-            else:
-                ordbuf.copy_(order[s * b : (s + n) * b])
-                run.run_many(n)
-            stop = False
-            for _ in range(n):
-                stop = self._after_step() or stop
-            done += n
-            s += n
-            if stop:
-                break
-        dt, self.last_host_dt = clock.stop()
-        (tot,) = ctx.sum_scalars(run.take_loss())
-        rows = done * b * ctx.world_size
-        return tot / max(rows * self.n_out, 1), rows, dt
+        if small_steps_path(eng, self.opt, self.ctx, cfg, b, Xd)[0]:
+            def fused(s, c):
+                at = slice(s * b, (s + c) * b)
+                X, Y, kw = (Xd[at], Yd[at], {}) if order is None else (Xd, Yd, {"rows": order[at]})
+                eng.fused_steps(X, Y, b, c, self.opt, self.grad_scale(b), loss_into=run.loss_acc, **kw)
+
+            return self.run_pass(run, small_schedule(steps, budget), fused, b)
+        warm = max(0, run.eager_steps + 2 - run.calls)  # (calls grows by one per step on every route)
+        return self.run_pass(run, pass_schedule(steps, n, warm, order is None, budget),
+                             replay_launcher(run, stage, n, warm, steps, order is None), b)
 
     def fit(self, train, val):
         cfg, ctx = self.cfg, self.ctx
@@ -549,38 +605,44 @@ class Trainer:
             t_ep = time.perf_counter()
             order = self._epoch_order(n, per_rank, dev)
             src = self._permuted(Xd, Yd, order) if per_rank // max(b, 1) <= MAX_SLICED_STEPS else None
-            if src is not None:  # this epoch's rows in shuffled order, read as contiguous slices
-                Xs, Ys = src
-            else:
-                Xs, Ys = Xd, Yd
             with trace_range("train_epoch", dev):
-                tr_loss, rows, dt = self.train_steps(Xs, Ys, order, b, sliced=src is not None)
-            self.eng.check_device_errors()  # once per epoch: a hand-off timed out in some step
-            with trace_range("evaluate", dev):
-                v_loss, v_mse = self.evaluate(*val)
-            self.epoch += 1
-            h = self.history
-            h.loss.append(tr_loss)
-            h.val_loss.append(v_loss)
-            h.val_mse.append(v_mse)
-            h.epoch_time.append(time.perf_counter() - t_ep)
-            hd = getattr(self, "last_host_dt", dt)
-            h.rows_per_s.append(rows / hd if hd > 0 else 0.0)
-            h.rows_per_s_device.append(rows / dt if dt > 0 else 0.0)
-            if cfg.verbose >= 2:
-                self.log(f"Epoch {self.epoch}/{cfg.epochs} - {h.epoch_time[-1]:.2f}s - loss: {tr_loss:.6f}"
-                         f" - val_loss: {v_loss:.6f} - val_mse: {v_mse:.6f} - rows/s: {h.rows_per_s[-1]:.0f}",
-                         flush=True)
-            self._log_metrics()
-            improved = v_loss < self.stopper.best
-            self.stopper.update(v_loss)
-            with trace_range("checkpoint", dev):
-                if improved and self.on_best is not None:
-                    ctx.barrier()
-                    if ctx.is_main:
-                        self.on_best(self)
-                    ctx.barrier()
-                self.save_state()
-            if cfg.max_steps and self.global_step >= cfg.max_steps:
+                # src: this epoch's rows in shuffled order, read in place as contiguous slices
+                result = self.train_steps(*src, b) if src is not None else self.train_steps(Xd, Yd, b, order)
+            if self.close_round(result, val, t_ep, lambda h: (
+                    f"Epoch {self.epoch}/{cfg.epochs} - {h.epoch_time[-1]:.2f}s - loss: {h.loss[-1]:.6f}"
+                    f" - val_loss: {h.val_loss[-1]:.6f} - val_mse: {h.val_mse[-1]:.6f}"
+                    f" - rows/s: {h.rows_per_s[-1]:.0f}")):
                 break
         return self.history
+
+    def close_round(self, result, val, t0: float, line) -> bool:
+        """Close an epoch (fit) or a stream chunk (fit_online) whose pass returned ``result`` and
+        which began at ``t0``: device-error check, validation, history, the verbose line
+        (``line(history)``: the caller's text), the metrics record, early stopping, the best-model
+        hook and the resumable state. True = training ends (early stop or max_steps)."""
+        cfg, ctx, dev = self.cfg, self.ctx, self.eng.device
+        tr_loss, rows, dt, host = result
+        self.eng.check_device_errors()  # once per round: a hand-off timed out in some step
+        with trace_range("evaluate", dev):
+            v_loss, v_mse = self.evaluate(*val)
+        self.epoch += 1
+        h = self.history
+        h.loss.append(tr_loss)
+        h.val_loss.append(v_loss)
+        h.val_mse.append(v_mse)
+        h.epoch_time.append(time.perf_counter() - t0)
+        h.rows_per_s.append(rows / host if host > 0 else 0.0)
+        h.rows_per_s_device.append(rows / dt if dt > 0 else 0.0)
+        if cfg.verbose >= 2:
+            self.log(line(h), flush=True)
+        self._log_metrics()
+        improved = v_loss < self.stopper.best
+        self.stopper.update(v_loss)
+        with trace_range("checkpoint", dev):
+            if improved and self.on_best is not None:
+                ctx.barrier()
+                if ctx.is_main:
+                    self.on_best(self)
+                ctx.barrier()
+            self.save_state()
+        return self.stopper.stopped or bool(cfg.max_steps and self.global_step >= cfg.max_steps)

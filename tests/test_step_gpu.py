@@ -233,12 +233,18 @@ def test_run_many_equals_single_replays(model):
     assert abs(lm - la) <= 3.0 * abs(lb - la) + 1e-5 * abs(la)
 
 
-def test_trainer_graph_steps_equal_single_steps(monkeypatch, tmp_path):
+@pytest.mark.parametrize("path", ["sliced", "indexed"])
+def test_trainer_graph_steps_equal_single_steps(monkeypatch, tmp_path, path):
     """The resident-data training loop (Trainer.train_steps) in groups
-    of WELLFLOW_GRAPH_STEPS steps per replay, rows from a static order buffer, against one
-    replay per step: the same loss history and test loss."""
+    of WELLFLOW_GRAPH_STEPS steps per replay against one replay per step: the same loss history
+    and test loss, with the epoch's rows read as contiguous slices of the materialised shuffle
+    (sliced) and through the static order buffer (indexed: the route of every epoch longer than
+    MAX_SLICED_STEPS steps, taken here by setting that bound to 0)."""
+    from wellflow.train import trainer
     from wellflow.train.job import run_job
 
+    if path == "indexed":
+        monkeypatch.setattr(trainer, "MAX_SLICED_STEPS", 0)
     names = "well,field,t,whp,choke,glr,temp,water_cut,dsp,flow"
     types = "string,string,int,float,float,float,float,float,float,float"
     res = {}

@@ -215,6 +215,150 @@ def test_sliced_epochs_bound_the_graph_count():
     assert "MAX_SLICED_STEPS" in src and "_permuted" in src
 
 
+INF = float("inf")
+
+
+def _singles(lo, hi):
+    return [(s, 1) for s in range(lo, hi)]
+
+
+def test_pass_schedule_literals():
+    """The replay path's launches, row by row as the loop issued them before the schedule was a
+    function of its own (eager_steps = 2: the first 4 - calls steps of a runner are singles), the
+    balanced group length, and the K-step path's launches."""
+    from wellflow.train.trainer import SMALL_STEPS_PER_LAUNCH as K, group_len, pass_schedule, small_schedule
+
+    rows = [  # steps, graph_steps, n, aligned, runner calls at entry, budget, schedule
+        (9, 8, 9, True, 0, INF, _singles(0, 9)),
+        (9, 8, 9, True, 9, INF, [(0, 9)]),
+        (20, 8, 10, True, 0, INF, _singles(0, 10) + [(10, 10)]),
+        (20, 8, 10, False, 0, INF, _singles(0, 4) + [(4, 10)] + _singles(14, 20)),
+        (20, 8, 10, False, 20, INF, [(0, 10), (10, 10)]),
+        (20, 8, 10, True, 20, 17, [(0, 10)] + _singles(10, 17)),
+        (13, 4, 5, True, 2, INF, _singles(0, 5) + [(5, 5)] + _singles(10, 13)),
+        (13, 4, 5, False, 2, INF, _singles(0, 2) + [(2, 5), (7, 5)] + _singles(12, 13)),
+    ]
+    for steps, gs, n, aligned, calls, budget, want in rows:
+        assert group_len(steps, gs, True) == n
+        assert pass_schedule(steps, n, max(0, 4 - calls), aligned, budget) == want, (steps, gs, aligned, calls)
+    assert [group_len(s, 8, True) for s in (12, 20, 2)] == [6, 10, 2]  # Python's round(): 1.5 -> 2, 2.5 -> 2
+    assert group_len(20, 8, False) == 1 and group_len(1, 8, True) == 8 and group_len(0, 8, True) == 8
+    # a pass entered with the budget spent: one single step on the replay path, none on the K-step path
+    assert pass_schedule(5, 1, 0, False, 0) == [(0, 1)] and pass_schedule(5, 5, 0, True, -2) == [(0, 1)]
+    assert small_schedule(5, 0) == [] and small_schedule(5, -2) == [] and small_schedule(0) == []
+    assert small_schedule(2 * K + 88) == [(0, K), (K, K), (2 * K, 88)]
+    assert small_schedule(2 * K + 88, K + 44) == [(0, K), (K, 44)] and small_schedule(3, 300) == [(0, 3)]
+
+
+def test_pass_schedule_properties():
+    """What fixes the replay schedule uniquely, over steps x group length x warm-up x alignment x
+    budget: the launches tile the pass from step 0 up to min(steps, budget), each is one step or a
+    whole group, and a group is taken exactly where one is allowed."""
+    from wellflow.train.trainer import group_len, pass_schedule
+
+    for steps in range(41):
+        for gs in (1, 2, 3, 4, 8):
+            n = group_len(steps, gs, True)
+            for warm in range(7):
+                for aligned in (True, False):
+                    for budget in (1, 5, 17, INF):
+                        at = 0
+                        for s, c in pass_schedule(steps, n, warm, aligned, budget):
+                            case = (steps, n, warm, aligned, budget, s, c)
+                            assert s == at and c in (1, n), case  # contiguous from 0, no overlap
+                            allowed = (n > 1 and s >= warm and s + n <= steps and s + n <= budget
+                                       and (not aligned or s % n == 0))
+                            assert (c == n) if allowed else (c == 1), case
+                            at += c
+                        assert at == min(steps, budget), (steps, n, warm, aligned, budget)
+
+
+class _RecordingRunner:
+    """Stands in for StepRunner: at each call it reads ``inputs`` as the captured step would and
+    records the dataset rows of every step of the launch (Y[i] == i, static index buffers
+    resolved at call time)."""
+    eager_steps, loss_acc = 2, None
+
+    def __init__(self, inputs):
+        self.inputs, self.calls, self.seen, self.prepared = inputs, 0, [], []
+
+    def _rows(self, key):
+        x, y, *rows = self.inputs(key)
+        return [int(v) for v in (y[rows[0]] if rows else y)]
+
+    def run(self, key=0):
+        self.calls += 1
+        self.seen.append(self._rows(key))
+
+    def run_many(self, n, key=0):
+        self.calls += n
+        self.seen.extend(self._rows((key, i)) for i in range(n))
+
+    def prepare_many(self, n, key=0):
+        self.prepared.append((n, key, len(self.seen), [self._rows((key, i)) for i in range(n)]))
+        return True
+
+    def take_loss(self):
+        return 0.0
+
+
+@pytest.mark.parametrize("budget", [INF, 7])
+@pytest.mark.parametrize("source,n,aligned,warm", [("sliced", 5, True, 5), ("indexed", 5, False, 2),
+                                                   ("gathered", 1, False, 0)])
+def test_each_step_trains_on_its_rows_whatever_the_schedule(source, n, aligned, warm, budget):
+    """Step j of a pass trains on rows order[j*b : (j+1)*b] of the dataset, through each batch
+    source and a schedule that mixes single steps and groups; the step count advances by the
+    steps run, max_steps ends the pass, and the sliced path prepares each aligned group's graph
+    exactly once, after the warm-up steps."""
+    from wellflow.parallel.dist import DistContext
+    from wellflow.train import trainer as T
+
+    b, steps, N = 4, 13, 64
+    order = torch.randperm(N, generator=torch.Generator().manual_seed(5))[: steps * b + 2]
+    X, Y = torch.arange(N * 3, dtype=torch.float32).reshape(N, 3), torch.arange(N, dtype=torch.float32)
+    idx, ordbuf = torch.zeros(b, dtype=torch.long), torch.zeros(n * b, dtype=torch.long)
+    if source == "sliced":
+        inputs, stage = T.sliced_source(X[order], Y[order], b)
+    elif source == "indexed":
+        inputs, stage = T.indexed_source(X, Y, order, b, idx, ordbuf)
+    else:
+        inputs, stage = T.gathered_source(X, Y, order, b, idx)
+    cfg = type("Cfg", (), {"patience": 3, "fail_at_step": -1, "max_steps": 0 if budget == INF else budget})()
+    eng = type("Eng", (), {"device": torch.device("cpu")})()
+    tr = T.Trainer(cfg, eng, None, DistContext(device="cpu"), "t")
+    run = _RecordingRunner(inputs)
+    launches = T.pass_schedule(steps, n, warm, aligned, budget)
+    if n > 1 and budget == INF:
+        assert {c for _, c in launches} == {1, n}  # singles and groups
+    loss, rows, dt, host = tr.run_pass(run, launches, T.replay_launcher(run, stage, n, warm, steps, aligned), b)
+    ran = min(steps, budget)
+    want = [order[j * b : (j + 1) * b].tolist() for j in range(steps)]
+    assert run.seen == want[:ran]
+    assert tr.global_step == ran == run.calls and rows == ran * b and dt > 0 and host > 0
+    if source == "sliced":
+        assert [p[:3] for p in run.prepared] == [(5, 0, warm), (5, 5, warm)]
+        assert [p[3] for p in run.prepared] == [want[0:5], want[5:10]]
+    else:
+        assert run.prepared == []
+
+
+def test_metrics_file_has_one_record_per_epoch_or_chunk(tmp_path):
+    """--metrics FILE: one JSON line per epoch (mlp) and per stream chunk (mlp_online), as
+    config.py documents, with ``epoch`` counting up from 1."""
+    import json
+
+    from wellflow.train.job import run_job
+
+    base = [NAMES, TYPES, "flow", str(tmp_path), "--synth-wells", "4", "--synth-steps", "200", "--device", "cpu",
+            "--mlp-hidden", "32,16", "--verbose", "0"]
+    for model, extra in (("mlp_online", ["--epochs", "1", "--online-chunk", "128"]), ("mlp", ["--epochs", "3"])):
+        path = tmp_path / f"{model}.jsonl"
+        out = run_job(model, base + extra + ["--metrics", str(path)], log=lambda *a, **k: None)
+        recs = [json.loads(ln) for ln in path.read_text().splitlines()]
+        assert out["epochs"] >= 3 and [r["epoch"] for r in recs] == list(range(1, out["epochs"] + 1))
+        assert [r["loss"] for r in recs] == out["history"]["loss"]
+
+
 def test_writeback_skips_sync_only_when_the_fused_update_covers_the_optimizer():
     """StepRunner leaves out sync_weights only when the engine's fused optimizer launch will
     actually run for this optimizer (round-5 ADVICE: an LSTM engine with a shadow-writing Adam
