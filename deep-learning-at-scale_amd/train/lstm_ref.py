@@ -274,6 +274,8 @@ class LstmState:
     grad_scale: float
     loss: str = "mse"
     clip: float = 6.0
+    grads0: torch.Tensor | None = None   # the flat bucket before the call (None: zero)
+    loss0: torch.Tensor | None = None    # the loss accumulator before the call (None: zero)
 
     @property
     def KX(self):
@@ -287,13 +289,25 @@ class LstmState:
         G, KA, H = 4 * self.H, self.KA, self.H
         return flat[: G * KA].view(G, KA), flat[G * KA: G * KA + H], flat[G * KA + H: G * KA + H + 1]
 
+    def prior(self):
+        """(gW0, gw_out0, gb_out0, loss0): what the bucket and the loss accumulator held before
+        the call, zeros where none was given."""
+        g0 = self.grads0 if self.grads0 is not None else torch.zeros_like(self.grads)
+        l0 = self.loss0 if self.loss0 is not None else torch.zeros_like(self.loss_sum)
+        return (*self.views(g0), l0.view(1))
+
     @classmethod
-    def of_engine(cls, eng, x, y, grad_scale):
-        """Snapshot (clones) of a NativeLSTM after forward_backward(x, y, grad_scale)."""
+    def of_engine(cls, eng, x, y, grad_scale, grads0=None, loss0=None, loss_acc=None):
+        """Snapshot (clones) of a NativeLSTM after forward_backward(x, y, grad_scale). ``grads0`` /
+        ``loss0``: the bucket and the accumulator as they were before a call that added to them
+        (zero_grads=False, loss_into=loss_acc); ``loss_acc``: the tensor that received the loss
+        (the engine's own ``loss_sum`` when None)."""
         c = lambda v: v.detach().clone()
+        o = lambda v: None if v is None else c(v).view(-1)
         return cls(eng.F, eng.H, eng.T, eng.B, c(eng.XH), c(eng.Wp), c(eng.WhhT), c(eng.Cst), c(eng.S),
-                   c(eng.DG), c(eng.pred), c(eng.dy), c(eng.loss_sum), c(eng.grads), c(eng.params),
-                   c(x), c(y), float(grad_scale), eng.loss_kind, float(eng.clip))
+                   c(eng.DG), c(eng.pred), c(eng.dy), c(eng.loss_sum if loss_acc is None else loss_acc).view(-1),
+                   c(eng.grads), c(eng.params), c(x), c(y), float(grad_scale), eng.loss_kind, float(eng.clip),
+                   o(grads0), o(loss0))
 
 
 def pack_x_ref(x: torch.Tensor, KX: int) -> torch.Tensor:
@@ -313,7 +327,7 @@ def _cap(chk: Check, cap: float, what: str):
 
 def check_forward(st: LstmState) -> list:
     """S[t], Cst[t+1] and the h block of XH[t+1] for every t, each from XH[t] and Wp as the
-    device left them; Cst slab 0 and the x blocks exact."""
+    device left them; Cst slab 0, the x blocks and h before step 0 (``h_init``) exact."""
     T, B, H, KX, KA = st.T, st.B, st.H, st.KX, st.KA
     XH = st.XH.view(T + 1, B, KA)
     Wp = st.Wp.view(4 * H, KA)
@@ -335,6 +349,9 @@ def check_forward(st: LstmState) -> list:
                           (within_bf16(XH[t + 1, :, KX:], r["h"], r["e_h"], "h", t), "h")):
             _cap(chk, CAP_FWD, f"{what}[{t}]")
             out.append(chk)
+    # h_{-1}: the h block of XH[0] is zeroed by the constructor and written by nothing after it;
+    # step 0 above follows the device's own XH[0], so this is the only check a stray store there meets
+    out.append(within_abs(XH[0, :, KX:], z0, 0.0, "h_init", 0))
     return out
 
 
@@ -353,25 +370,55 @@ def loss_dy_ref(pred, y, grad_scale, loss, clip):
 def check_head(st: LstmState) -> list:
     """pred within the dot-product bound ``(H + 1) u (|h| . |w| + |b|)``; dy against the loss formula
     applied in fp32 to the device's own pred: exact for clipped MAE, within 2^-24 |dy| (at most one
-    fp32 ulp) for MSE; loss_sum / gw_out / gb_out within their sum bounds ``n u sum|terms|``."""
-    T, B, H, KX, KA = st.T, st.B, st.H, st.KX, st.KA
-    hT = st.XH.view(T + 1, B, KA)[T, :, KX:].double()
-    _, w_out, b_out = st.views(st.params)
-    _, gw_out, gb_out = st.views(st.grads)
-    w = w_out.double()
-    pred = hT @ w + b_out.double()
-    e_pred = (H + 1) * U32 * (hT.abs() @ w.abs() + b_out.double().abs())
-    out = [within_abs(st.pred, pred, e_pred, "pred")]
+    fp32 ulp) for MSE; loss_sum / gw_out / gb_out within their sum bounds ``n u sum|terms|``.
+    With a prior (``grads0`` / ``loss0``) each of the three sums is ``prior + sum``: the prior is one
+    more term of the same bound, and the adds that reach the word count as further roundings."""
+    out = [check_pred(st)]
     dy, terms = loss_dy_ref(st.pred, st.y.float(), st.grad_scale, st.loss, st.clip)
     # dy: clipped MAE exactly (a sign times the scale, or 0: nothing rounds); MSE within 1 fp32
     # ulp, taken as 2^-24 relative (the spacing of fp32 numbers is at least that)
     e_dy = 0.0 if st.loss != "mse" else 2.0 ** -24 * dy.double().abs()
     out.append(within_abs(st.dy, dy, e_dy, "dy"))
-    out.append(within_abs(st.loss_sum, terms.sum().view(1), (B + 4) * U32 * terms.sum(), "loss_sum"))
-    d = st.dy.double()
-    out.append(within_abs(gw_out, d @ hT, (B + 1) * U32 * (d.abs() @ hT.abs()), "gw_out"))
-    out.append(within_abs(gb_out, d.sum().view(1), B * U32 * d.abs().sum(), "gb_out"))
+    _, gw_out, gb_out = st.views(st.grads)
+    for name, dev in (("loss_sum", st.loss_sum), ("gw_out", gw_out), ("gb_out", gb_out)):
+        prior, s, a, n = head_terms(st)[name]
+        out.append(within_abs(dev, prior + s, n * U32 * (prior.abs() + a), name))
     return out
+
+
+def check_pred(st: LstmState) -> Check:
+    T, B, H, KX, KA = st.T, st.B, st.H, st.KX, st.KA
+    hT = st.XH.view(T + 1, B, KA)[T, :, KX:].double()
+    _, w_out, b_out = st.views(st.params)
+    w = w_out.double()
+    pred = hT @ w + b_out.double()
+    e_pred = (H + 1) * U32 * (hT.abs() @ w.abs() + b_out.double().abs())
+    return within_abs(st.pred, pred, e_pred, "pred")
+
+
+def head_adds(B: int) -> tuple:
+    """Adds that reach (the loss word, a gw_out / gb_out word) on the loosest route: one atomic per
+    workgroup, and no launcher starts more workgroups than rows. csrc/elementwise.hip: launch_loss
+    caps its grid at 1024 blocks (launch_head_fwd at 512, launch_head_fwd_bwd at 128);
+    launch_head_fwd_bwd and launch_head_bwd_w both cap theirs at 128."""
+    return min(B, 1024), min(B, 128)
+
+
+def head_terms(st: LstmState) -> dict:
+    """name -> (prior, sum, sum of |terms|, n) of loss_sum, gw_out and gb_out in float64; the bound
+    of each is ``n u (|prior| + sum|terms|)``. Without a prior n is the term count the bound always
+    had; with one it grows by :func:`head_adds`."""
+    T, B, KX, KA = st.T, st.B, st.KX, st.KA
+    hT = st.XH.view(T + 1, B, KA)[T, :, KX:].double()
+    _, terms = loss_dy_ref(st.pred, st.y.float(), st.grad_scale, st.loss, st.clip)
+    d = st.dy.double()
+    _, gw0, gb0, l0 = st.prior()
+    nl, ng = head_adds(B)
+    xl = nl if st.loss0 is not None else 0
+    xg = ng if st.grads0 is not None else 0
+    return {"loss_sum": (l0.double(), terms.sum().view(1), terms.sum().view(1), B + 4 + xl),
+            "gw_out": (gw0.double(), d @ hT, d.abs() @ hT.abs(), B + 1 + xg),
+            "gb_out": (gb0.double(), d.sum().view(1), d.abs().sum().view(1), B + xg)}
 
 
 def check_backward(st: LstmState) -> list:
@@ -399,23 +446,45 @@ def check_backward(st: LstmState) -> list:
 
 
 def check_dw(st: LstmState) -> list:
-    """gW against sum_{t,b} DG^T XH of the device's own DG and XH; its padding columns 0."""
-    T, B, H, KX, KA, F = st.T, st.B, st.H, st.KX, st.KA, st.F
+    """gW against prior + sum_{t,b} DG^T XH of the device's own DG and XH; its padding columns
+    equal the prior exactly (0 without one)."""
+    F, KX = st.F, st.KX
+    gW, _, _ = st.views(st.grads)
+    prior, s, a, n = dw_terms(st)
+    chk = within_abs(gW, prior + s, n * U32 * (prior.abs() + a), "gW")
+    if st.T * st.B <= 1024:  # against the gradient alone: a prior must not raise the cap
+        _cap(chk, CAP_GW * float(s.abs().max()), "gW")
+    return [chk, within_abs(gW[:, F + 1: KX], prior[:, F + 1: KX], 0.0, "gW_pad")]
+
+
+def dw_adds(T: int) -> int:
+    """Adds that reach a gW word on the loosest route: one per split-K partial (atomics, or the
+    slab reduce's ``out[i] += ...``) of every dW launch. models/lstm.py picks at most 32 splits
+    (``min(32, K // 16384)``); the side-stream route launches ceil(T / chunk) chunks of
+    ``max(1, splits * chunk // T)`` splits each, which is at most 2 * 32 where that quotient is
+    at least one and at most T chunks of one split where it is not."""
+    return max(64, T)
+
+
+def dw_terms(st: LstmState) -> tuple:
+    """(prior, sum, sum of |terms|, n) of gW in float64; the bound is ``n u (|prior| + sum|terms|)``.
+    n = T B without a prior, as the bound always had; with one it grows by :func:`dw_adds`."""
+    T, B, H, KA = st.T, st.B, st.H, st.KA
     A = st.DG.view(T * B, 4 * H).double()
     X = st.XH.view(T + 1, B, KA)[:T].reshape(T * B, KA).double()
-    gW, _, _ = st.views(st.grads)
-    ref = A.t() @ X
-    e = T * B * U32 * (A.abs().t() @ X.abs())
-    chk = within_abs(gW, ref, e, "gW")
-    if T * B <= 1024:
-        _cap(chk, CAP_GW * float(ref.abs().max()), "gW")
-    pad = gW[:, F + 1: KX]
-    return [chk, within_abs(pad, torch.zeros_like(pad, dtype=torch.float64), 0.0, "gW_pad")]
+    gW0 = st.prior()[0].double()
+    return gW0, A.t() @ X, A.abs().t() @ X.abs(), T * B + (dw_adds(T) if st.grads0 is not None else 0)
 
 
 def check_all(st: LstmState, dw: bool = True) -> list:
     out = check_forward(st) + check_head(st) + check_backward(st)
     return out + check_dw(st) if dw else out
+
+
+def check_inference(st: LstmState) -> list:
+    """What ``forward`` / ``forward_windows`` leave: every forward step and pred (``st.x`` is the
+    batch as packed, zero padding rows included). dy, the loss and the gradients are not its."""
+    return check_forward(st) + [check_pred(st)]
 
 
 def violations(checks) -> list:

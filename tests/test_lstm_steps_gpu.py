@@ -7,10 +7,10 @@ the state out after each call and checks every step from the device's own inputs
 head and the weight gradient within their dot-product bounds. The path each case is meant to
 take is asserted, not assumed: the persistent flags, ``persistent_error() == 0`` and, from the
 STAT block's launch and workgroup totals, the (sub-batches, units per workgroup) instantiation
-that ``persistent_split`` picks (mirrored below), which pins the NC / NRT variant.
+that ``persistent_split`` picks (mirrored in tests/lstm_plans.py), which pins the NC / NRT variant.
 
 tests/test_lstm_steps_cpu.py proves the checker: an fp32 emulation passes under the caps and
-nine mutations of the state are each rejected where they were made.
+its mutations of the state are each rejected where they were made.
 """
 import json
 
@@ -19,52 +19,14 @@ import torch
 
 from wellflow.train import lstm_ref as R
 
+from lstm_plans import _cus, bwd_plan, dw_uses_slab, fwd_plan
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 
 
-# ------------------------------------------------------------------ the launchers' rules
-def persistent_split(B, row_quantum, max_units, cols, cus, unit_mask):
-    """csrc/lstm_persistent.hip persistent_split: the fewest equal sub-batches, then the fewest
-    units per workgroup, whose grid fits one workgroup per CU. -> (nsub, units) or None."""
-    for nsub in range(1, 65):
-        if B % nsub or (B // nsub) % row_quantum:
-            continue
-        Bs = B // nsub
-        u = 1
-        while u <= max_units:
-            if (unit_mask >> (u.bit_length() - 1)) & 1 and Bs % (row_quantum * u) == 0 \
-                    and Bs // (row_quantum * u) * cols <= cus:
-                return nsub, u
-            u *= 2
-    return None
-
-
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def fwd_plan(B, H, F):
-    """launch_lstm_fwd_persistent: (nsub, NC, grid) or None (per-step kernels)."""
-    KX = (F + 1 + 63) // 64 * 64
-    KA = KX + H
-    if B % 32 or KX not in (64, 128) or H not in (128, 256, 512) or B * KA * 2 >= 2 ** 31 - 1:
-        return None
-    NB = 4 * H // 256
-    p = persistent_split(B, 32, 8, NB, _cus(), 0x9 if KA // 32 == 20 else 0xF)
-    return None if p is None else (p[0], p[1], B // p[0] // (32 * p[1]) * NB)
-
-
-def bwd_plan(B, H):
-    """launch_lstm_bwd_persistent (T >= 2): (nsub, units = NRT / 4, grid) or None."""
-    if B % 64 or H not in (128, 256, 512) or B * 4 * H * 2 >= 2 ** 31 - 1:
-        return None
-    NB = H // 64
-    p = persistent_split(B, 64, 4, NB, _cus(), 0xF)
-    return None if p is None else (p[0], p[1], B // p[0] // (64 * p[1]) * NB)
-
-
+# the launchers' rules (which persistent instantiation, which dW route): tests/lstm_plans.py
 def smallest_batch(pred, step):
     for B in range(step, 1 << 17, step):
         if pred(B):
@@ -237,23 +199,6 @@ def test_persistent_backward_every_units_variant(H, units):
 
 
 # ------------------------------------------------------------------ dW routes
-def dw_uses_slab(G, KA, K, ksplit, slab_numel):
-    """csrc/gemm.hip launch_gemm / launch_dw_288w: only the 256x288 tile (KA % 288 == 0) knows the
-    slab; it clamps the split to one workgroup per CU, steps it down until 64 * nsplit divides K
-    (equal_ksplit), and stores partials into the slab when more than one split remains and all of
-    them fit (the engine's gW has ldo == KA). Otherwise fp32 atomics."""
-    if KA % 288 or slab_numel is None:
-        return False
-    tiles = (G // 256) * (KA // 288)
-    cus = _cus()
-    ks = max(1, ksplit)
-    if ks * tiles > cus and cus // tiles >= 1:
-        ks = cus // tiles
-    while ks > 1 and K % (64 * ks):
-        ks -= 1
-    return ks > 1 and ks * G * KA <= slab_numel and (G * KA) % 4 == 0
-
-
 @pytest.mark.parametrize("H", [512, 128, 256])
 @pytest.mark.parametrize("route", ["ksplit0", "ksplit3_slab", "atomics", "chunk2"])
 def test_dw_routes(H, route):
