@@ -1297,6 +1297,76 @@ void group_sums(const at::Tensor& pred, const at::Tensor& order, const at::Tenso
   TORCH_CHECK(ok, "group_sums: the launcher refused the shape");
 }
 
+// Conformal scores (quantile.hip): out[i] = (float)|d|, or (float)(|d| / |v|) with `relative`, for
+// v = pred * y_scale + y_shift and d = v - y in fp64. pred / y / out contiguous fp32 [M] (views of
+// larger vectors allowed); out does not overlap pred / y. Stream-ordered; nothing is read back here.
+void abs_scores(const at::Tensor& pred, const at::Tensor& y, double y_scale, double y_shift, bool relative,
+                const at::Tensor& out) {
+  for (const at::Tensor* t : {&pred, &y, &out}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 1,
+                "abs_scores: pred / y / out must be contiguous fp32 GPU vectors");
+    TORCH_CHECK(t->device() == pred.device(), "abs_scores: tensors on different devices");
+  }
+  const int64_t M = pred.numel();
+  TORCH_CHECK(M >= 1 && y.numel() == M && out.numel() == M, "abs_scores: pred holds ", M, " elements, y ", y.numel(),
+              ", out ", out.numel(), " (need the same, >= 1)");
+  const char* o0 = static_cast<const char*>(out.data_ptr());
+  for (const at::Tensor* t : {&pred, &y}) {
+    const char* a0 = static_cast<const char*>(t->data_ptr());
+    TORCH_CHECK(a0 + 4 * M <= o0 || o0 + 4 * M <= a0, "abs_scores: out overlaps pred / y");
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(pred.device());
+  const bool ok = wf::launch_abs_scores(pred.data_ptr<float>(), y.data_ptr<float>(), M, y_scale, y_shift, relative,
+                                        out.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(ok, "abs_scores: the launcher refused the shape");
+}
+
+// Exact per-group order statistics (quantile.hip): out[g][a] = the ranks[g][a]-th smallest score of
+// group g, from the host-built plan of ops/native.py QuantilePlan: order int32 [M], pieces int32
+// [2][P], piece_group int32 [P], hist int32 [G][A][256] (zero; left zero), state int32 [G][A][2].
+// ranks int32 [G][A], out fp32 [G][A]. Stream-ordered; nothing is read back here.
+void group_quantiles(const at::Tensor& scores, const at::Tensor& order, const at::Tensor& pieces,
+                     const at::Tensor& piece_group, const at::Tensor& ranks, const at::Tensor& hist,
+                     const at::Tensor& state, const at::Tensor& out) {
+  TORCH_CHECK(scores.defined() && scores.is_cuda() && scores.scalar_type() == at::kFloat && scores.is_contiguous() &&
+                  scores.dim() == 1,
+              "group_quantiles: scores must be a contiguous fp32 GPU vector");
+  const int64_t M = scores.numel();
+  TORCH_CHECK(M >= 1 && M <= INT32_MAX, "group_quantiles: ", M, " scores (need 1 .. 2^31 - 1)");
+  for (const at::Tensor* t : {&order, &pieces, &piece_group, &ranks, &hist, &state}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                "group_quantiles: order / pieces / piece_group / ranks / hist / state must be contiguous int32 GPU tensors");
+  }
+  TORCH_CHECK(order.dim() == 1 && order.numel() == M, "group_quantiles: the plan orders ", order.numel(),
+              " scores, scores holds ", M);
+  TORCH_CHECK(pieces.dim() == 2 && pieces.size(0) == 2 && pieces.size(1) >= 1, "group_quantiles: pieces must be int32 [2][P]");
+  const int64_t P = pieces.size(1);
+  TORCH_CHECK(piece_group.dim() == 1 && piece_group.numel() == P, "group_quantiles: piece_group must be int32 [", P, "]");
+  TORCH_CHECK(ranks.dim() == 2 && ranks.size(0) >= 1 && ranks.size(1) >= 1, "group_quantiles: ranks must be int32 [G][A]");
+  const int64_t G = ranks.size(0), A = ranks.size(1);
+  TORCH_CHECK(A <= wf::kQuantMaxLevels, "group_quantiles: ", A, " levels (at most ", wf::kQuantMaxLevels, ")");
+  TORCH_CHECK(G * A <= wf::kQuantMaxCells, "group_quantiles: ", G, " groups x ", A, " levels (at most ",
+              wf::kQuantMaxCells, " cells)");
+  TORCH_CHECK(P <= M + G, "group_quantiles: ", P, " pieces for ", M, " scores in ", G, " groups");
+  TORCH_CHECK(hist.dim() == 3 && hist.size(0) == G && hist.size(1) == A && hist.size(2) == 256,
+              "group_quantiles: hist must be int32 [", G, "][", A, "][256]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(hist.data_ptr()) % 16 == 0, "group_quantiles: hist must be 16-byte aligned");
+  TORCH_CHECK(state.dim() == 3 && state.size(0) == G && state.size(1) == A && state.size(2) == 2,
+              "group_quantiles: state must be int32 [", G, "][", A, "][2]");
+  TORCH_CHECK(out.defined() && out.is_cuda() && out.scalar_type() == at::kFloat && out.is_contiguous() &&
+                  out.dim() == 2 && out.size(0) == G && out.size(1) == A,
+              "group_quantiles: out must be a contiguous fp32 [", G, "][", A, "] GPU tensor");
+  for (const at::Tensor* t : {&order, &pieces, &piece_group, &ranks, &hist, &state, &out}) {
+    TORCH_CHECK(t->device() == scores.device(), "group_quantiles: tensors on different devices");
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(scores.device());
+  const bool ok = wf::launch_group_quantiles(scores.data_ptr<float>(), order.data_ptr<int>(), pieces.data_ptr<int>(),
+                                             pieces.data_ptr<int>() + P, piece_group.data_ptr<int>(), M, (int)P, (int)G,
+                                             (int)A, ranks.data_ptr<int>(), hist.data_ptr<int>(), state.data_ptr<int>(),
+                                             out.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(ok, "group_quantiles: the launcher refused the shape");
+}
+
 void im2col1d(const at::Tensor& x, int64_t B, int64_t L, int64_t Cin, int64_t ksz, int64_t Kp,
               const at::Tensor& col) {
   check_t(x, at::kFloat, "x");
@@ -1622,6 +1692,8 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(group_sums);
   WF_DEF(attr_step);
   WF_DEF(solve_step);
+  WF_DEF(abs_scores);
+  WF_DEF(group_quantiles);
   // host-only queries (no launch; callable without a GPU)
   m.def("diag_build", &diag_build);
   m.def("gemm_plan", &gemm_plan);

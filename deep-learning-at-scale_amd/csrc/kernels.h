@@ -485,4 +485,26 @@ constexpr int kSolveRefine = 2;
 bool launch_solve_step(const float* p, const float* want, long M, double y_scale, double y_shift, int mode,
                        const float* grid_x, float* xs, double* fs, int* status, hipStream_t s);
 
+// ---- conformal scores (quantile.hip) ----
+// v = (double)pred * y_scale + y_shift, d = v - (double)y (err_sums' d); out[i] = (float)fabs(d), or
+// with `relative` (float)(fabs(d) / fabs(v)) under IEEE rules; fp64 never contracted, one
+// round-to-nearest-even cast: bitwise equal to the numpy rule. M >= 1 elements, one thread per
+// element, plain loads and stores. false = refused, nothing launched.
+bool launch_abs_scores(const float* pred, const float* y, long M, double y_scale, double y_shift, bool relative,
+                       float* out, hipStream_t s);
+
+// ---- exact per-group order statistics (quantile.hip) ----
+// out[g][a] = the ranks[g][a]-th smallest (0-based, clamped into [0, n_g - 1]) of the scores of group
+// g, bit for bit numpy's sort order for scores that are non-negative or NaN (NaN last); NaN for an
+// empty group. The plan is launch_group_sums' (order, piece_first, piece_len) plus piece_group int32
+// [pieces], the group of every piece. A radix select over the scores' bit patterns: four rounds of
+// 8 bits, two stream-ordered launches each. hist int32 [G][A][256]: zero before the first launch,
+// left zero by every call; state int32 [G][A][2] (prefix, remaining rank): written before it is
+// read. Integer atomics only: bitwise repeatable. false = refused, nothing launched.
+constexpr int kQuantMaxLevels = 4;
+constexpr int kQuantMaxCells = 16384;  // G * A: hist is at most 16 MiB
+bool launch_group_quantiles(const float* scores, const int* order, const int* piece_first, const int* piece_len,
+                            const int* piece_group, long M, int pieces, int G, int A, const int* ranks, int* hist,
+                            int* state, float* out, hipStream_t s);
+
 }  // namespace wf

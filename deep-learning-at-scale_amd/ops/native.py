@@ -420,6 +420,90 @@ def group_sums(pred, plan: GroupPlan, y_scale: float, y_shift: float, out, slot:
                      plan.scratch)
 
 
+def abs_scores(pred, y, y_scale: float, y_shift: float, relative: bool, out):
+    """``out[i] = float32(|d|)``, with ``relative`` ``float32(|d| / |v|)``, for ``v = pred * y_scale +
+    y_shift`` and ``d = v - y`` in uncontracted fp64 (csrc/quantile.hip; the rule is
+    wellflow/interval.py's ``score_host``, bit for bit): the conformal scores of a calibration pass.
+    ``pred`` / ``y`` / ``out``: contiguous fp32 device vectors [M]; ``out`` does not overlap the
+    other two. Stream-ordered; nothing comes back to the host."""
+    import torch
+
+    named = (("pred", pred), ("y", y), ("out", out))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"abs_scores: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if pred.dim() != 1 or pred.numel() < 1:
+        raise ValueError(f"abs_scores: pred {tuple(pred.shape)} must be a non-empty vector")
+    for name, t in named[1:]:
+        if t.shape != pred.shape:
+            raise ValueError(f"abs_scores: {name} {tuple(t.shape)} must have pred's shape {tuple(pred.shape)}")
+    if pred.device.type != "cuda" or any(t.device != pred.device for _, t in named):
+        raise ValueError("abs_scores: the tensors must be on one GPU, got " + ", ".join(str(t.device) for _, t in named))
+    for name, t in named:
+        if not t.is_contiguous():
+            raise ValueError(f"abs_scores: {name} must be contiguous")
+    for name, t in named[:2]:
+        if _spans_overlap(t, out):
+            raise ValueError(f"abs_scores: out overlaps {name}")
+    lib().abs_scores(pred, y, float(y_scale), float(y_shift), bool(relative), out)
+
+
+QUANTILE_MAX_LEVELS = 4  # csrc/kernels.h kQuantMaxLevels
+QUANTILE_MAX_CELLS = 16384  # csrc/kernels.h kQuantMaxCells: hist is G x A x 1 KiB, at most 16 MiB
+
+
+class QuantilePlan:
+    """How :func:`group_quantiles` selects ``A`` order statistics in each of ``G`` groups of M
+    scores: a :class:`GroupPlan` of the ids (``groups``: built once on the host, as for the grouped
+    sums), the group of every piece on the device (``piece_group``), and the select's working
+    memory: ``hist`` int32 [G][A][256], zero here and left zero by every call, and ``state`` int32
+    [G][A][2] (the key prefix and the remaining rank of a (group, level), written before it is
+    read). ``1 <= A <= QUANTILE_MAX_LEVELS`` and ``G * A <= QUANTILE_MAX_CELLS``."""
+
+    def __init__(self, ids, G: int, A: int, device):
+        import torch
+
+        G, A = int(G), int(A)
+        if not 1 <= A <= QUANTILE_MAX_LEVELS:
+            raise ValueError(f"group_quantiles: {A} levels (need 1 .. {QUANTILE_MAX_LEVELS})")
+        if G < 1 or G * A > QUANTILE_MAX_CELLS:
+            raise ValueError(f"group_quantiles: {G} groups x {A} levels = {G * A} histograms (need 1 .. "
+                             f"{QUANTILE_MAX_CELLS}: 1 KiB each, 16 MiB in all)")
+        self.groups = GroupPlan(ids, G, device)
+        self.G, self.A, self.M, self.device, self.counts = G, A, self.groups.M, self.groups.device, self.groups.counts
+        self.piece_group = torch.from_numpy(self.groups.piece_group).to(self.device)
+        self.hist = torch.zeros((G, A, 256), dtype=torch.int32, device=self.device)
+        self.state = torch.zeros((G, A, 2), dtype=torch.int32, device=self.device)
+
+
+def group_quantiles(scores, plan: QuantilePlan, ranks, out):
+    """``out[g][a]`` = the ``ranks[g][a]``-th smallest (0-based, clamped into the group) of the scores
+    of group ``g`` of ``plan``, exactly (csrc/quantile.hip): ``np.sort`` per group bit for bit for
+    scores that are non-negative or NaN (NaN sorts last); NaN for an empty group. ``scores`` fp32
+    device vector [plan.M], ``ranks`` int32 [plan.G][plan.A] and ``out`` fp32 [plan.G][plan.A] on the
+    plan's device. Integer atomics only: bitwise repeatable; a NaN score moves only its own group's
+    answers. Stream-ordered; nothing comes back to the host."""
+    import torch
+
+    if not isinstance(plan, QuantilePlan):
+        raise TypeError("group_quantiles: plan must be a QuantilePlan")
+    for name, t, dt in (("scores", scores, torch.float32), ("ranks", ranks, torch.int32), ("out", out, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError(f"group_quantiles: {name} must be a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.device != plan.device:
+            raise ValueError(f"group_quantiles: {name} is on {t.device}, the plan on {plan.device}")
+    if scores.dim() != 1 or scores.numel() != plan.M or not scores.is_contiguous():
+        raise ValueError(f"group_quantiles: scores holds {tuple(scores.shape)} scores, the plan groups {plan.M}")
+    for name, t in (("ranks", ranks), ("out", out)):
+        if tuple(t.shape) != (plan.G, plan.A) or not t.is_contiguous():
+            raise ValueError(f"group_quantiles: {name} must be contiguous [{plan.G}][{plan.A}] (groups x levels), "
+                             f"got {tuple(t.shape)}")
+    if _spans_overlap(scores, out):
+        raise ValueError("group_quantiles: out overlaps scores")
+    g = plan.groups
+    lib().group_quantiles(scores, g.order, g.pieces, plan.piece_group, ranks, plan.hist, plan.state, out)
+
+
 def gemm(A, B, M, N, K, *, a_mn=False, lda=None, b_mn=False, ldb=None, outF=None, outH=None,
          ldo=None, bias=None, mask=None, ldm=None, mask_scale=1.0, colsum=None, alpha=1.0,
          beta=0.0, act=0, atomic=False, ksplit=1, drop_p=0.0, seed=0, tile=0, seed_dev=None):

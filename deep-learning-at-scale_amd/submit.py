@@ -20,6 +20,11 @@ units that, added to a base value, give the prediction (wellflow/explain.py).
 ``python -m wellflow.submit setpoint <model> columnNames columnTypes targetColumn storagePath dataPath --column C --want V``
 searches, row by row, the value of one continuous input column at which the model predicts the wanted
 value (``--want-column COL``: one wanted value per row): the inverse of predict (wellflow/setpoint.py).
+
+``python -m wellflow.submit interval <model> columnNames columnTypes targetColumn storagePath dataPath [--calibrate]``
+puts a band around every prediction: ``--calibrate`` scores held-out rows and writes, per ``--by`` group and
+level ``--alpha``, the conformal quantile of the residuals; without it the bands are read back and written next
+to the predictions as ``lower_<L>`` / ``upper_<L>`` (wellflow/interval.py).
 """
 import sys
 
@@ -51,6 +56,10 @@ def main(argv=None) -> int:
         from .setpoint import main as setpoint_main
 
         return setpoint_main(argv[1:])
+    if argv[0] == "interval":  # conformal prediction bands: calibrate on held-out rows, then apply next to the predictions
+        from .interval import main as interval_main
+
+        return interval_main(argv[1:])
     run_job(argv[0], argv[1:])
     return 0
 
