@@ -379,6 +379,26 @@ class Trainer:
 
     # ------------------------------------------------------------------ state
     def state_dict(self) -> dict:
+        """The resumable training state. On a GPU the job's device state falls into four classes
+        (declared attribute by attribute in train/state_ref.py STATE_CLASSES, held to it by
+        tests/test_resume_gpu.py):
+
+        * carried — written by a step, read by a later one: ``params``, the optimizer's ``m`` /
+          ``v`` / ``vel``, the device step count ``step_dev[0]`` (read back here through
+          ``steps_taken``), the CNN's dropout counter ``rng``, the gradient bucket (all zero
+          between steps under ``zero_grads``). Saved here, except ``rng``: it equals
+          ``global_step`` on every route (eager step, one-step graph, n-step graph, K steps per
+          launch, the GEMM path's host-side add), and load_state_dict restores it from that.
+        * rebuilt — pure functions of ``params``, the bf16 operand images the kernels read:
+          NativeMLP ``shadow`` / ``w2t``, NativeLSTM ``Wp`` / ``WhhT``, NativeCNN ``WcA`` / ``WdF``
+          / ``WdB`` (``shadow`` on the GEMM path). Not saved: a running job gets them from the
+          fused updates, a resumed one from ``sync_weights``, and the two agree bit for bit.
+        * scratch — fully written before it is read within one step or launch (activations, DG,
+          dout, partials, slabs, pred, dy, loss_sum, clip scratch, staging buffers). Not saved.
+        * constructor constants and synchronisation — sync words, tickets (``step_dev[1]``),
+          launch epochs, STAT blocks, the zero h_init block of ``XH[0]``: a fresh engine has them
+          right. ``clip_state[0]`` (the factor) is recomputed before every read; ``clip_state[1:4]``
+          are per-epoch statistics and deliberately not carried over a resume."""
         return {
             "name": self.name,
             "epoch": self.epoch,
