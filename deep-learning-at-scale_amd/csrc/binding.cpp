@@ -816,6 +816,39 @@ bool mlp2_forward(const at::Tensor& X, int64_t Fp, const at::Tensor& W1, const a
                              opt_ptr<float>(red, at::kFloat, "red", wf::kMlpRedFloats));
 }
 
+// Fused MLP scoring forward for wide inputs (mlp_wide.hip): 8 <= Fp <= 512, inference only; writes
+// pred[0 .. B) and nothing else. Shapes and operands the launcher does not take are refused here,
+// with a message, before anything is launched.
+void mlp2_forward_wide(const at::Tensor& X, int64_t Fp, const at::Tensor& W1, const at::Tensor& b1,
+                       const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3,
+                       const at::Tensor& pred, int64_t B) {
+  constexpr int64_t H = 256;
+  TORCH_CHECK(Fp % 8 == 0 && Fp >= 8 && Fp <= wf::kMlpWideMaxFp, "mlp2_forward_wide: Fp = ", Fp,
+              " (needs a multiple of 8 in 8 .. ", wf::kMlpWideMaxFp, ")");
+  TORCH_CHECK(B > 0 && B <= INT32_MAX, "mlp2_forward_wide: B = ", B, " rows");
+  for (const at::Tensor* t : {&X, &W1, &W2}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous(),
+                "mlp2_forward_wide: X, W1, W2 must be contiguous bf16 GPU tensors");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "mlp2_forward_wide: bf16 operands must be 16-B aligned");
+  }
+  check_extent(X, B * Fp, "X");
+  check_extent(W1, H * Fp, "W1");
+  check_extent(W2, H * H, "W2");
+  for (const at::Tensor* t : {&b1, &b2, &w3}) {
+    check_t(*t, at::kFloat, "bias/w3");
+    check_extent(*t, H, "bias/w3");
+  }
+  check_t(b3, at::kFloat, "b3");
+  check_extent(b3, 1, "b3");
+  check_t(pred, at::kFloat, "pred");
+  check_extent(pred, B, "pred");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
+  TORCH_CHECK(wf::launch_mlp2_fwd_wide(bfp(X), (int)Fp, bfp(W1), fp(b1), bfp(W2), fp(b2), fp(w3), fp(b3), fp(pred),
+                                       (int)B, cur_stream()),
+              "mlp2_forward_wide: the launcher refused the shape");
+}
+
 // head forward + MSE + head weight gradient in one pass over H (elementwise.hip); false = shape
 // not covered (the caller runs head_fwd + head_bwd_w)
 bool head_fwd_bwd(const at::Tensor& Hm, int64_t ldh, int64_t B, int64_t Hd, const at::Tensor& w, const at::Tensor& b0,
@@ -1651,6 +1684,8 @@ PYBIND11_MODULE(_C, m) {
   m.doc() = "wellflow HIP kernel library (gfx950)";
   WF_DEF(gemm);
   WF_DEF(mlp2_forward);
+  WF_DEF(mlp2_forward_wide);
+  m.attr("MLP_WIDE_ROWS") = wf::kMlpWideRows;  // the wide forward's row tile
   WF_DEF(mlp2_backward);
   WF_DEF(mlp2_dw2);
   WF_DEF(mlp2_reduce);

@@ -208,6 +208,18 @@ bool launch_mlp2_fwd(const bf16_t* X, int Fp, const bf16_t* W1, const float* b1,
 // Mask mode (M2 != nullptr; needs y, dw3, db3): H2 is NOT written — only its ReLU bitmask M2
 // ([B][8] u32, bit u of row r = word 8r + u / 32, bit u % 32) — and dw3 += H2^T dy,
 // db3 += sum dy are accumulated by the forward itself.
+
+// ---- fused MLP scoring forward for wide inputs (mlp_wide.hip): Fp (% 8 == 0, 8 .. 512) -> 256 ->
+// 256 -> 1, inference only. X [B][Fp] bf16, W1 [256][Fp] / W2 [256][256] bf16 (K-contiguous),
+// b1 / b2 / w3 / b3 fp32; writes pred[0 .. B) and nothing else (H1, H2 never leave the CU; no
+// atomics, no scratch). Rounding points are the per-layer route's (bf16 H1 and H2, fp32 head);
+// a row's prediction does not depend on B or on its position. Returns false (nothing launched)
+// for other Fp, B <= 0 or a bf16 operand that is not 16-B aligned.
+constexpr int kMlpWideRows = 128;   // rows per workgroup tile
+constexpr int kMlpWideMaxFp = 512;  // = ASSEMBLE_MAX_F (features.hip)
+bool launch_mlp2_fwd_wide(const bf16_t* X, int Fp, const bf16_t* W1, const float* b1, const bf16_t* W2,
+                          const float* b2, const float* w3, const float* b3, float* pred, int B, hipStream_t s);
+
 // ---- fused MLP backward (mlp_fused.hip), everything but the dW2 GEMM: from H1, H2
 // ([B][256] bf16), dy, w3 / W2 and X: dZ2 ([B][256] bf16, dW2's operand), db1, db2, dw3, db3
 // and — when dW1 != nullptr — dW1 ([256][Fp], Fp <= 32) (fp32, accumulated with atomics);

@@ -193,6 +193,7 @@ class NativeMLP(Engine):
         # (tests/test_engines_gpu.py flips them); no environment variable reaches them any more.
         self.x_inplace = True       # bf16 batches read in place (no D2D copy into self.X)
         self.fused = True           # weight-stationary fused forward (False: per-layer GEMMs)
+        self.wide_fwd = True        # 64 < Fp <= 512: the fused scoring forward (False: per-layer GEMMs)
         self.fused_bwd = True       # fused backward (False: per-layer GEMMs)
         self.mask_h2 = True         # H2 leaves the forward only as a ReLU bitmask
         self.dw_ksplit, self.dw_tile = 0, 0  # split-K / tile overrides of the weight-gradient GEMMs
@@ -363,9 +364,21 @@ class NativeMLP(Engine):
                                          self.Hs[0] if store_h1 else None, self.Hs[1], self.pred, dy, loss_sum,
                                          float(dy_scale), B, m2, dw3, db3, rows, red))
 
+    def _wide_forward(self, B: int) -> bool:
+        """Scoring forward for 64 < Fp <= 512 in ONE launch (csrc/mlp_wide.hip): X streams
+        through an LDS ring, W1 from L2, W2 in registers; H1 and H2 never reach HBM, only
+        ``pred[:B]`` is written. Same rounding points as the per-layer route; a row's prediction
+        does not depend on the batch around it. False = not covered (the per-layer GEMMs run)."""
+        if not (self.fused and self.wide_fwd and self.hidden == (256, 256) and 64 < self.Fp <= 512):
+            return False
+        wl, _, _ = self.lay.views(self.shadow)
+        pl, hw, hb = self.lay.views(self.params)
+        self._C.mlp2_forward_wide(self._Xop, self.Fp, wl[0][0], pl[0][1], wl[1][0], pl[1][1], hw, hb, self.pred, B)
+        return True
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         B = self._load_x(x)
-        if self._fused_forward(B, store_h1=False):
+        if self._fused_forward(B, store_h1=False) or self._wide_forward(B):
             return self.pred[:B]
         self._forward_body(B)
         _, hw, hb = self.lay.views(self.params)

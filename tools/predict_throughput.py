@@ -13,8 +13,10 @@ the same machine state:
   per-value label lookup of the host path dominates its total.
 * the assembly kernel alone: achieved GB/s (bytes read + written, from the shapes) next to a
   device-to-device copy moving the same byte count.
+* ``--wide-forward`` (instead of the above): ``NativeMLP.forward`` over N resident bf16 rows at
+  Fp = 72, 128, 256, 512, the fused wide kernel (csrc/mlp_wide.hip) against the per-layer route.
 
-    python tools/predict_throughput.py [--rows N] [--rounds R] [--json PATH]
+    python tools/predict_throughput.py [--rows N] [--rounds R] [--json PATH] [--wide-forward]
 """
 from __future__ import annotations
 
@@ -157,23 +159,62 @@ def bench_kernel(pipe, table, rounds, launches=20):
     return out
 
 
+def bench_wide_forward(rows, rounds, widths=(72, 128, 256, 512), launches=5):
+    """``NativeMLP.forward`` over ``rows`` resident bf16 rows at Fp > 64: the fused wide kernel
+    (csrc/mlp_wide.hip) against the per-layer route (``wide_fwd=False``: two GEMMs + head_fwd) on
+    the same engine, windows interleaved; X bytes/s = rows * Fp * 2 over the call time."""
+    from wellflow.models.mlp import NativeMLP, init_mlp_flat
+
+    dev = torch.device("cuda", 0)
+    out = {}
+    for F in widths:
+        eng = NativeMLP(F, (256, 256), rows, device=dev, params=init_mlp_flat(F).to(dev))
+        X = eng.to_input_format(torch.randn(rows, F, device=dev))
+        t = {True: [], False: []}
+        pred = {}
+        for wide in (True, False):  # warm-up, and the outputs to compare
+            eng.wide_fwd = wide
+            pred[wide] = eng.forward(X).clone()
+        for _ in range(rounds):
+            for wide in (True, False):
+                eng.wide_fwd = wide
+                t[wide].append(_events(lambda: eng.forward(X), launches))
+        tw, tp = _median(t[True]), _median(t[False])
+        out[f"Fp{eng.Fp}"] = {"rows": rows, "Fp": eng.Fp, "wide_ms": tw * 1e3, "per_layer_ms": tp * 1e3,
+                              "per_layer_over_wide": tp / tw, "wide_x_GBps": rows * eng.Fp * 2 / tw / 1e9,
+                              "per_layer_x_GBps": rows * eng.Fp * 2 / tp / 1e9,
+                              "wide_rows_per_s": rows / tw, "per_layer_rows_per_s": rows / tp,
+                              "max_abs_diff": (pred[True] - pred[False]).abs().max().item(),
+                              "pred_abs_max": pred[False].abs().max().item(),
+                              "all_wide_ms": [round(v * 1e3, 4) for v in t[True]],
+                              "all_per_layer_ms": [round(v * 1e3, 4) for v in t[False]]}
+        del eng, X, pred
+        torch.cuda.empty_cache()
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rows", type=int, default=2_097_152)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--json", default="")
     ap.add_argument("--skip-lstm", action="store_true")
+    ap.add_argument("--wide-forward", action="store_true",
+                    help="only the MLP forward at Fp = 72, 128, 256, 512: fused wide kernel vs per-layer route")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("predict_throughput: needs a GPU (no rate is reported without one)", file=sys.stderr)
         return 2
     rec = {"device": torch.cuda.get_device_name(0)}
     with tempfile.TemporaryDirectory() as tmp:
-        rec["mlp"], (pipe, table) = bench_mlp(args.rows, args.rounds, tmp)
-        rec["assemble_kernel"] = bench_kernel(pipe, table, max(args.rounds, 5))
-        del table
-        if not args.skip_lstm:
-            rec["lstm"] = bench_lstm(args.rounds, tmp)
+        if args.wide_forward:
+            rec["mlp_wide_forward"] = bench_wide_forward(args.rows, args.rounds)
+        else:
+            rec["mlp"], (pipe, table) = bench_mlp(args.rows, args.rounds, tmp)
+            rec["assemble_kernel"] = bench_kernel(pipe, table, max(args.rounds, 5))
+            del table
+            if not args.skip_lstm:
+                rec["lstm"] = bench_lstm(args.rounds, tmp)
     line = json.dumps(rec)
     print(line)
     if args.json:
