@@ -849,6 +849,57 @@ void mlp2_forward_wide(const at::Tensor& X, int64_t Fp, const at::Tensor& W1, co
               "mlp2_forward_wide: the launcher refused the shape");
 }
 
+// The wide forward as a training step's first launch (mlp_wide.hip mlp2_fwd_wide_train_kernel):
+// writes pred, dy, H1, the H2 ReLU bitmask M2 and, with rows, the gathered batch Xout; adds the
+// loss sum and the head gradients. clip > 0: clipped MAE, else MSE. Refusals as mlp2_forward_wide.
+void mlp2_forward_wide_train(const at::Tensor& X, int64_t Fp, const at::Tensor& W1, const at::Tensor& b1,
+                             const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3,
+                             const at::Tensor& y, c10::optional<at::Tensor> rows, c10::optional<at::Tensor> Xout,
+                             const at::Tensor& H1, const at::Tensor& M2, const at::Tensor& pred, const at::Tensor& dy,
+                             const at::Tensor& dw3, const at::Tensor& db3, const at::Tensor& loss_sum, double dy_scale,
+                             double clip, int64_t B) {
+  constexpr int64_t H = 256;
+  const bool indexed = rows.has_value() && rows->defined();
+  const bool has_out = Xout.has_value() && Xout->defined();
+  TORCH_CHECK(Fp % 8 == 0 && Fp >= 8 && Fp <= wf::kMlpWideMaxFp, "mlp2_forward_wide_train: Fp = ", Fp,
+              " (needs a multiple of 8 in 8 .. ", wf::kMlpWideMaxFp, ")");
+  TORCH_CHECK(B > 0 && B <= INT32_MAX, "mlp2_forward_wide_train: B = ", B, " rows");
+  TORCH_CHECK(!indexed || has_out, "mlp2_forward_wide_train: rows needs Xout (the dense copy of the gathered batch)");
+  std::vector<const at::Tensor*> ops = {&X, &W1, &W2, &H1};
+  if (has_out) ops.push_back(&*Xout);
+  for (const at::Tensor* t : ops) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous(),
+                "mlp2_forward_wide_train: X, W1, W2, H1, Xout must be contiguous bf16 GPU tensors");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "mlp2_forward_wide_train: bf16 operands must be 16-B aligned");
+  }
+  const int64_t nrows = check_x_rows(X, Fp, B, rows);
+  check_extent(W1, H * Fp, "W1");
+  check_extent(W2, H * H, "W2");
+  check_extent(H1, B * H, "H1");
+  if (has_out) check_extent(*Xout, B * Fp, "Xout");
+  for (const at::Tensor* t : {&b1, &b2, &w3, &dw3}) {
+    check_t(*t, at::kFloat, "bias/w3/dw3");
+    check_extent(*t, H, "bias/w3/dw3");
+  }
+  for (const at::Tensor* t : {&b3, &db3, &loss_sum}) {
+    check_t(*t, at::kFloat, "b3/db3/loss_sum");
+    check_extent(*t, 1, "b3/db3/loss_sum");
+  }
+  check_t(y, at::kFloat, "y");
+  check_extent(y, nrows, "y");  // y is indexed like X
+  for (const at::Tensor* t : {&pred, &dy}) {
+    check_t(*t, at::kFloat, "pred/dy");
+    check_extent(*t, B, "pred/dy");
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
+  TORCH_CHECK(wf::launch_mlp2_fwd_wide_train(bfp(X), (int)Fp, bfp(W1), fp(b1), bfp(W2), fp(b2), fp(w3), fp(b3), fp(y),
+                                             rows_ptr(rows, B), nrows, has_out ? bfp(*Xout) : nullptr, bfp(H1),
+                                             mask_ptr(M2, B), fp(pred), fp(dy), fp(dw3), fp(db3), fp(loss_sum),
+                                             (float)dy_scale, (float)clip, (int)B, cur_stream()),
+              "mlp2_forward_wide_train: the launcher refused the shape");
+}
+
 // head forward + MSE + head weight gradient in one pass over H (elementwise.hip); false = shape
 // not covered (the caller runs head_fwd + head_bwd_w)
 bool head_fwd_bwd(const at::Tensor& Hm, int64_t ldh, int64_t B, int64_t Hd, const at::Tensor& w, const at::Tensor& b0,
@@ -1685,6 +1736,7 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(gemm);
   WF_DEF(mlp2_forward);
   WF_DEF(mlp2_forward_wide);
+  WF_DEF(mlp2_forward_wide_train);
   m.attr("MLP_WIDE_ROWS") = wf::kMlpWideRows;  // the wide forward's row tile
   WF_DEF(mlp2_backward);
   WF_DEF(mlp2_dw2);

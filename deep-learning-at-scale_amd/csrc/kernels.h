@@ -219,6 +219,22 @@ constexpr int kMlpWideRows = 128;   // rows per workgroup tile
 constexpr int kMlpWideMaxFp = 512;  // = ASSEMBLE_MAX_F (features.hip)
 bool launch_mlp2_fwd_wide(const bf16_t* X, int Fp, const bf16_t* W1, const float* b1, const bf16_t* W2,
                           const float* b2, const float* w3, const float* b3, float* pred, int B, hipStream_t s);
+// The same forward as a TRAINING step's first launch (mlp2_fwd_wide_train_kernel): beyond pred it
+// writes H1 ([B][256] bf16: dW2's operand and the backward's layer-1 ReLU mask), the H2 ReLU
+// bitmask M2 ([B][8] u32, launch_mlp2_fwd's mask-mode layout; H2 itself never leaves the CU),
+// dy[0 .. B) and adds the head gradients dw3 += H2^T dy, db3 += sum dy and the loss sum (one fp32
+// atomic per unit / sum and workgroup). clip > 0: clipped MAE (loss min(|d|, clip),
+// dy = dy_scale sign(d) [|d| <= clip]), else MSE (d^2, dy = dy_scale d); d = pred - y.
+// rows (optional, int64): batch row gr is dataset row rows[gr] of X and y, clamped into
+// [0, nrows); the gathered batch is then also stored dense into Xout ([B][Fp] bf16, the dW1
+// GEMM's operand). Without rows Xout is not touched. launch_mlp2_bwd (H1, M2, dW1 == nullptr)
+// consumes the result. Returns false (nothing launched) for Fp % 8 != 0, Fp outside 8 .. 512,
+// B <= 0, a misaligned bf16 operand, rows without Xout, or a missing output.
+bool launch_mlp2_fwd_wide_train(const bf16_t* X, int Fp, const bf16_t* W1, const float* b1, const bf16_t* W2,
+                                const float* b2, const float* w3, const float* b3, const float* y,
+                                const long long* rows, long nrows, bf16_t* Xout, bf16_t* H1, unsigned* M2, float* pred,
+                                float* dy, float* dw3, float* db3, float* loss_sum, float dy_scale, float clip, int B,
+                                hipStream_t s);
 
 // ---- fused MLP backward (mlp_fused.hip), everything but the dW2 GEMM: from H1, H2
 // ([B][256] bf16), dy, w3 / W2 and X: dZ2 ([B][256] bf16, dW2's operand), db1, db2, dw3, db3

@@ -194,6 +194,7 @@ class NativeMLP(Engine):
         self.x_inplace = True       # bf16 batches read in place (no D2D copy into self.X)
         self.fused = True           # weight-stationary fused forward (False: per-layer GEMMs)
         self.wide_fwd = True        # 64 < Fp <= 512: the fused scoring forward (False: per-layer GEMMs)
+        self.wide_step = True       # 64 < Fp <= 512: the fused training forward (False: per-layer GEMMs + head)
         self.fused_bwd = True       # fused backward (False: per-layer GEMMs)
         self.mask_h2 = True         # H2 leaves the forward only as a ReLU bitmask
         self.dw_ksplit, self.dw_tile = 0, 0  # split-K / tile overrides of the weight-gradient GEMMs
@@ -376,6 +377,60 @@ class NativeMLP(Engine):
         self._C.mlp2_forward_wide(self._Xop, self.Fp, wl[0][0], pl[0][1], wl[1][0], pl[1][1], hw, hb, self.pred, B)
         return True
 
+    def _wide_step_ok(self) -> bool:
+        """A training step of 64 < Fp <= 512 features takes the fused forward (_step_wide)."""
+        return (self.fused and self.wide_step and self.hidden == (256, 256) and 64 < self.Fp <= 512
+                and self.loss_kind in ("mse", "mae_clip"))
+
+    def _dw_ksplit(self, h: int, k: int, B: int) -> int:
+        """Split-K of the weight-gradient GEMM dW [h][k] over a batch of B rows. These GEMMs have a
+        tiny M x N (a few 128 x 128 tiles) and K = batch: split K so the grid has ~512 workgroups,
+        each reducing >= 256 rows, but keep the fp32 atomic traffic (ksplit x h x k x 4 B) <= ~16 MB.
+        256 x 256 at B = 262144: split-K 64 = 256 workgroups, one per CU (tools/gpu.sh sweep:
+        0.421 ms/step at split-K 32 -> 0.390 at 64, 0.404 at 128). ``dw_ksplit`` overrides."""
+        if self.dw_ksplit > 0:
+            return max(1, min(self.dw_ksplit, B // 256))
+        tiles = ((h + 127) // 128) * ((k + 127) // 128)
+        return max(1, min(512 // tiles, B // 256, 64, (16 << 20) // (4 * h * k)))
+
+    def _step_wide(self, x, y, rows, grad_scale: float, zero_grads: bool, loss_into=None) -> torch.Tensor:
+        """Training step for 64 < Fp <= 512: the fused forward (csrc/mlp_wide.hip: H1, the H2
+        bitmask, pred, dy, loss and head gradients in ONE launch; with ``rows`` the dataset is read
+        in place and the gathered batch lands in ``self.X``) -> the fused backward in mask mode
+        (dZ2, dZ1, bias gradients) -> the dW2 and dW1 split-K GEMMs. H2 never reaches HBM. Four
+        launches, no host sync, no allocation."""
+        from ..ops.native import gemm
+
+        C = self._C
+        if rows is not None:
+            B, Xin, Xop = rows.shape[0], x.view(-1), self.X
+        else:
+            B = self._load_x(x)
+            Xin = Xop = self._Xop
+        y = y.contiguous().float()
+        if zero_grads:
+            self.grads.zero_()
+        ls = loss_into if loss_into is not None else self.loss_sum
+        if loss_into is None:
+            self.loss_sum.zero_()
+        wl, _, _ = self.lay.views(self.shadow)
+        pl, hw, hb = self.lay.views(self.params)
+        gl, ghw, ghb = self.lay.views(self.grads)
+        mae = self.loss_kind == "mae_clip"  # mlp2_step's convention: dy_scale = grad_scale (MAE) or 2 grad_scale
+        C.mlp2_forward_wide_train(Xin, self.Fp, wl[0][0], pl[0][1], wl[1][0], pl[1][1], hw, hb, y, rows,
+                                  self.X if rows is not None else None, self.Hs[0], self.M2, self.pred, self.dy,
+                                  ghw, ghb, ls, (1.0 if mae else 2.0) * float(grad_scale),
+                                  float(self.clip) if mae else 0.0, B)
+        self._Xop, self._Xop_rows = Xop, B
+        if not C.mlp2_backward(self.Hs[0], self.Hs[1], self.dy, hw, wl[1][0], Xop, self.Fp, self.dZ[0], self.dZ[1],
+                               None, gl[0][1], gl[1][1], ghw, ghb, B, self.M2, None, None, None, None):
+            raise RuntimeError("NativeMLP: the fused backward refused the wide step")
+        for l, prevH in ((1, self.Hs[0]), (0, Xop)):  # as the fallback loop of forward_backward calls them
+            h, k = self.lay.dims[l]
+            gemm(self.dZ[l], prevH, h, k, B, a_mn=True, lda=h, b_mn=True, ldb=k,
+                 outF=gl[l][0], atomic=True, ksplit=self._dw_ksplit(h, k, B), tile=self.dw_tile)
+        return ls
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         B = self._load_x(x)
         if self._fused_forward(B, store_h1=False) or self._wide_forward(B):
@@ -479,6 +534,13 @@ class NativeMLP(Engine):
         from ..ops.native import gemm
 
         C = self._C
+        if self._wide_step_ok():
+            if rows is not None and not (x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 2
+                                         and x.shape[1] == self.Fp and x.data_ptr() % 16 == 0
+                                         and rows.shape[0] <= self.B):
+                # a table the kernel cannot read in place: gather first, as the Fp <= 64 route does
+                x, y, rows = x.index_select(0, rows), y.index_select(0, rows), None
+            return self._step_wide(x, y, rows, grad_scale, zero_grads, loss_into)
         if rows is not None:
             B = rows.shape[0]
             if (self._recompute_ok(B) and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[1] == self.Fp
@@ -528,23 +590,14 @@ class NativeMLP(Engine):
         if not fused_bwd:
             C.head_bwd_w(self.Hs[-1], H, B, H, self.dy, ghw, ghb)
             C.head_bwd_x(self.Hs[-1], H, B, H, self.dy, hw, True, self.dZ[-1], H, gl[-1][1])
-        # dW GEMMs have tiny M x N (a few 128x128 tiles) and K = batch: split K so the
-        # grid has ~512 workgroups, each reducing >= 256 rows
-        tiles = lambda h, k: ((h + 127) // 128) * ((k + 127) // 128)  # noqa: E731
         for l in range(L - 1, -1, -1):
             if l == 0 and fused_bwd and fused_dw1:
                 break  # dW1 accumulated inside the fused backward
             h, k = self.lay.dims[l]
             prevH = self.Hs[l - 1] if l > 0 else self._Xop
-            # dW_l = dZ_l^T H_{l-1}   (reduce over the batch; MN-contiguous operands)
-            # ... but keep the fp32 atomic traffic (ksplit x h x k x 4 B) <= ~16 MB. 256 x 256 at
-            # B = 262144: split-K 64 = 256 workgroups, one per CU (tools/gpu.sh sweep:
-            # 0.421 ms/step at split-K 32 -> 0.390 at 64, 0.404 at 128)
-            ksplit = max(1, min(512 // tiles(h, k), B // 256, 64, (16 << 20) // (4 * h * k)))
-            if self.dw_ksplit > 0:
-                ksplit = max(1, min(self.dw_ksplit, B // 256))
+            # dW_l = dZ_l^T H_{l-1}   (reduce over the batch; MN-contiguous operands; _dw_ksplit)
             gemm(self.dZ[l], prevH, h, k, B, a_mn=True, lda=h, b_mn=True, ldb=k,
-                 outF=gl[l][0], atomic=True, ksplit=ksplit, tile=self.dw_tile)
+                 outF=gl[l][0], atomic=True, ksplit=self._dw_ksplit(h, k, B), tile=self.dw_tile)
             if l > 0 and not fused_bwd:
                 # dZ_{l-1} = (dZ_l W_l) * [H_{l-1} > 0];  db_{l-1} = colsum
                 gemm(self.dZ[l], wl[l][0], B, k, h, b_mn=True, ldb=k, outH=self.dZ[l - 1],
