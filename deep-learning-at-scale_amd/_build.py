@@ -45,8 +45,10 @@ HIPCC_FLAGS = [
 # agreement with float64 on exact data. The current compiler selects none in this file either
 # way (same registers, LDS and scratch with and without; profiles/r8/mlp_wide_forward/README.md),
 # so the flag costs nothing today and keeps a later compiler from introducing them.
+_NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
-    "mlp_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "mlp_wide.hip": _NO_PACKED_F32,
+    "mlp_f32.hip": _NO_PACKED_F32,  # the same contract, in fp32 end to end
 }
 
 

@@ -79,7 +79,7 @@ class RunConfig:
     dropout: float = 0.5
     # runtime
     device: str = "auto"         # auto | cpu | cuda
-    precision: str = "bf16"      # bf16 (native MFMA path) | fp32 (torch oracle)
+    precision: str = "bf16"      # bf16 (native MFMA path) | fp32 (torch oracle) | fp32-native (scoring only)
     comm_dtype: str = "fp32"     # C2 gradient all-reduce precision: fp32 | bf16 (parallel/dist.py)
     group_col: str = ""          # series id column for windowing (default: first string col)
     # windowed models (lstm, cnn): "time" = contiguous per-series blocks in time order with a
@@ -150,7 +150,9 @@ def build_parser(model: str) -> argparse.ArgumentParser:
     ap.add_argument("--mlp-hidden", type=_tuple_ints, dest="mlp_hidden")
     ap.add_argument("--dropout", type=float)
     ap.add_argument("--device", choices=["auto", "cpu", "cuda"])
-    ap.add_argument("--precision", choices=["bf16", "fp32"])
+    ap.add_argument("--precision", choices=["bf16", "fp32", "fp32-native"],
+                    help="bf16: the native engine; fp32: the PyTorch oracle; fp32-native: the native fp32 forward "
+                         "(scoring jobs of mlp / mlp_online on a GPU only)")
     ap.add_argument("--comm-dtype", dest="comm_dtype", choices=["fp32", "bf16"],
                     help="data-parallel gradient all-reduce precision (default fp32)")
     ap.add_argument("--group-col", dest="group_col")
@@ -163,6 +165,16 @@ def build_parser(model: str) -> argparse.ArgumentParser:
     ap.add_argument("--verbose", type=int)
     ap.add_argument("--metrics", dest="metrics_path", help="append per-epoch JSON lines here")
     return ap
+
+
+SCORING_ONLY_PRECISION = "fp32-native"
+
+
+def refuse_scoring_only_precision(cfg: "RunConfig") -> None:
+    """A training job stops here, before any work, when it is given the scoring-only precision."""
+    if cfg.precision == SCORING_ONLY_PRECISION:
+        raise ValueError(f"--precision {SCORING_ONLY_PRECISION} is for scoring only (predict, importance, response, "
+                         f"explain, setpoint, interval): train with --precision bf16 or fp32")
 
 
 def parse_argv(model: str, argv) -> RunConfig:

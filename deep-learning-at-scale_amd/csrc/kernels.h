@@ -236,6 +236,18 @@ bool launch_mlp2_fwd_wide_train(const bf16_t* X, int Fp, const bf16_t* W1, const
                                 float* dy, float* dw3, float* db3, float* loss_sum, float dy_scale, float clip, int B,
                                 hipStream_t s);
 
+// ---- fused fp32 MLP scoring forward (mlp_f32.hip): F (>= 1, padded to Fp = 8 ceil(F / 8) <= 512)
+// -> 256 -> 256 -> 1 with fp32 operands and fp32 accumulation (v_mfma_f32_32x32x2_f32), inference
+// only. X [B][ldx] fp32 with ldx >= F and rows 4-B aligned only (columns >= F and rows >= B are
+// never read); W1 [256][Fp], W2 [256][256], b1 / b2 / w3 / b3 fp32, the views of the master
+// weights (16-B aligned). Writes pred[0 .. B) and nothing else (H1, H2 never leave the CU; no
+// atomics, no scratch); a row's prediction does not depend on B or on its position. Returns false
+// (nothing launched) for F < 1, Fp > 512, ldx < F, B <= 0 or a misaligned operand.
+constexpr int kMlpF32Rows = 64;    // rows per workgroup tile
+constexpr int kMlpF32MaxFp = 512;  // = ASSEMBLE_MAX_F (features.hip)
+bool launch_mlp2_fwd_f32(const float* X, long ldx, int F, const float* W1, const float* b1, const float* W2,
+                         const float* b2, const float* w3, const float* b3, float* pred, int B, hipStream_t s);
+
 // ---- fused MLP backward (mlp_fused.hip), everything but the dW2 GEMM: from H1, H2
 // ([B][256] bf16), dy, w3 / W2 and X: dZ2 ([B][256] bf16, dW2's operand), db1, db2, dw3, db3
 // and — when dW1 != nullptr — dW1 ([256][Fp], Fp <= 32) (fp32, accumulated with atomics);

@@ -441,6 +441,36 @@ class NativeMLP(Engine):
         self._C.head_fwd(self.Hs[-1], H, B, H, hw, hb, None, self.pred, None, None, 0.0)
         return self.pred[:B]
 
+    def f32_reason(self) -> str | None:
+        """None when :meth:`forward_f32` serves this engine's shape, else why not."""
+        if self.hidden != (256, 256):
+            return f"hidden {self.hidden} is not the fused (256, 256) shape"
+        if self.Fp > 512:
+            return f"{self.Fp} padded input features > 512"
+        return None
+
+    def forward_f32(self, X: torch.Tensor) -> torch.Tensor:
+        """Scoring forward in fp32 end to end, ONE launch (csrc/mlp_f32.hip): ``X`` is an fp32
+        ``[b][ldx]`` device tensor (``ldx >= F``; what the fp32 device assembly writes) read in
+        place, the weights are the fp32 master copy ``params`` (never the bf16 shadow). Only
+        ``pred[:b]`` is written: no training buffer is touched and H1, H2 never reach HBM."""
+        why = self.f32_reason()
+        if why is not None:
+            raise ValueError(f"NativeMLP.forward_f32: {why}")
+        if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype == torch.float32 and X.is_contiguous()):
+            raise ValueError("NativeMLP.forward_f32: X must be a contiguous fp32 [b][ldx] tensor (no copy, no cast "
+                             "is made)")
+        b, ldx = X.shape
+        if X.device != self.params.device:  # (an indexed device, where self.device may be plain "cuda")
+            raise ValueError(f"NativeMLP.forward_f32: X is on {X.device}, the engine on {self.params.device}")
+        if not 1 <= b <= self.B:
+            raise ValueError(f"NativeMLP.forward_f32: {b} rows (the engine's batch holds 1 .. {self.B})")
+        if ldx < self.F:
+            raise ValueError(f"NativeMLP.forward_f32: rows of {ldx} values < {self.F} features")
+        pl, hw, hb = self.lay.views(self.params)
+        self._C.mlp2_forward_f32(X, ldx, self.F, pl[0][0], pl[0][1], pl[1][0], pl[1][1], hw, hb, self.pred, b)
+        return self.pred[:b]
+
     def _recompute_ok(self, B: int) -> bool:
         """The H1-free training step: fused forward writes only the H2 bitmask, the fused
         backward and the dW2 kernel recompute H1 = relu(X W1^T + b1) from X (csrc/mlp_fused.hip)."""

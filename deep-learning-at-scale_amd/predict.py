@@ -72,6 +72,11 @@ class Predictor:
         self.cfg: RunConfig | None = None
         self.seq_len, self.group_col = 0, ""
         self.piece_rows = 0  # rows of the assembled MLP table per piece (0: what fits in 1/8 of HBM; scoring.py)
+        self.f32 = False  # --precision fp32-native: fp32 rows and NativeMLP.forward_f32 (scoring.py MlpPass)
+
+    @staticmethod
+    def _no_f32(why: str) -> str:
+        return f"--precision fp32-native: {why} (--precision fp32 scores in fp32 through the PyTorch oracle)"
 
     # ------------------------------------------------------------------ loading
     @classmethod
@@ -91,9 +96,16 @@ class Predictor:
             # an indexed device: the engines compare tensors' devices with their own (the MLP's
             # in-place input path, the LSTM's window ids), and "cuda" != "cuda:0"
             dev = torch.device("cuda", torch.cuda.current_device())
-        self = cls(name, schema, extra, dev, dev.type == "cuda" and precision == "bf16", batch)
+        f32 = precision == "fp32-native"
+        self = cls(name, schema, extra, dev, dev.type == "cuda" and (precision == "bf16" or f32), batch)
         if name == "gilbert":
             return self
+        if f32:  # the native engine's fp32 forward (csrc/mlp_f32.hip): the MLPs on a GPU, or an error
+            if dev.type != "cuda":
+                raise ValueError(cls._no_f32("it runs on a GPU only, the device is the CPU"))
+            if name not in ("mlp", "mlp_online"):
+                raise ValueError(cls._no_f32(f"it serves mlp and mlp_online, not {name}"))
+            self.f32 = True
         if extra.get("features") is None:
             raise ValueError(f"{mdl_path} holds no feature-pipeline state (extra['features']): it was not written "
                              f"by a training job, so new data cannot be encoded the way the model was trained")
@@ -107,6 +119,11 @@ class Predictor:
             if k != "n_features":
                 setattr(cfg, k, v)
         self.cfg, self.n_features = cfg, shp["n_features"]
+        if self.f32 and tuple(shp["mlp_hidden"]) != (256, 256):
+            raise ValueError(self._no_f32(f"the saved model's hidden layers are {tuple(shp['mlp_hidden'])}, the kernel's "
+                                          f"(256, 256)"))
+        if self.f32 and _round_up(self.n_features, 8) > 512:
+            raise ValueError(self._no_f32(f"the table has {self.n_features} features, the kernel takes 512"))
         # the univariate CNN reads the target's own history: its "feature" is the target series
         self.pipe = FeaturePipeline.from_state(schema, extra["features"],
                                                n_features=None if name == "cnn" else self.n_features)

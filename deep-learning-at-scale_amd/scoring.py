@@ -7,7 +7,8 @@ its batch, the piece size, the preallocated device buffers and the choice betwee
 routes:
 
 * device assembly (native engine, F <= ``ASSEMBLE_MAX_F``): csrc/features.hip builds the engine's
-  input rows from the raw columns; the MLP reads ``[chunk][Fp]`` bf16 slices of a piece in place,
+  input rows from the raw columns; the MLP reads ``[chunk][Fp]`` bf16 slices of a piece in place
+  (``--precision fp32-native``: ``[chunk][n_features]`` fp32 slices, :meth:`NativeMLP.forward_f32`),
   the LSTM reads its windows in place from the fp32 row table (:meth:`NativeLSTM.forward_windows`);
 * host assembly with the native engine (wider tables): ``FeaturePipeline.features`` builds the rows,
   they are uploaded, and the same device loop scores them;
@@ -203,12 +204,19 @@ class MlpPass(_Pass):
         self.rows = None
         if not self.native:
             return
-        dev, B, Fp = pred.device, self.B, self.eng.Fp
+        dev, B = pred.device, self.B
+        # --precision fp32-native: [piece][n_features] fp32 rows, as the fp32 assembly and the host
+        # pipeline write them, scored by NativeMLP.forward_f32; else [piece][Fp] bf16 rows
+        self.f32 = bool(getattr(pred, "f32", False))
+        if self.f32:
+            self.dtype, width = torch.float32, pred.n_features
+        else:
+            width = self.eng.Fp
         limit = piece_rows if piece_rows > 0 else \
-            torch.cuda.get_device_properties(dev).total_memory // HBM_TABLE_FRACTION // (Fp * 2)
+            torch.cuda.get_device_properties(dev).total_memory // HBM_TABLE_FRACTION // (width * self.dtype.itemsize)
         piece = max(B, limit // B * B)
         self.pieces = [(a, min(n, a + piece)) for a in range(0, n, piece)]
-        self.X = torch.empty((min(piece, n), Fp), dtype=torch.bfloat16, device=dev)
+        self.X = torch.empty((min(piece, n), width), dtype=self.dtype, device=dev)
         self.p = torch.empty(n, device=dev)
         if self.on_device:
             self.codes, self.cont = self.pipe.raw_columns(table)
@@ -216,13 +224,14 @@ class MlpPass(_Pass):
                 self.res = self._resident(self.codes, self.cont)
 
     def _input_format(self, X):
-        return self.eng.to_input_format(X)
+        return X if self.f32 else self.eng.to_input_format(X)  # the pipeline's fp32 rows go up unchanged
 
     def forward(self, X: torch.Tensor, a: int = 0) -> None:
         """The assembled piece ``X`` that starts at row ``a`` -> ``p[a : a + len(X)]``."""
         B, m = self.B, X.shape[0]
+        fwd = self.eng.forward_f32 if self.f32 else self.eng.forward
         for c in range(0, m, B):  # [chunk][Fp] slices read in place; the last one may be short
-            self.p[a + c : a + min(c + B, m)].copy_(self.eng.forward(X[c : c + B]))
+            self.p[a + c : a + min(c + B, m)].copy_(fwd(X[c : c + B]))
 
     def _score_host(self, X: np.ndarray) -> np.ndarray:
         X, B = torch.from_numpy(X), self.B

@@ -17,7 +17,7 @@ import time
 
 import torch
 
-from ..config import RunConfig, parse_argv
+from ..config import RunConfig, parse_argv, refuse_scoring_only_precision
 from ..data.pipeline import prepare
 from ..data.schema import parse_schema
 from ..models import registry
@@ -123,6 +123,7 @@ def run_job(model: str, argv, log=print) -> dict:
 
 
 def run_config(cfg: RunConfig, log=print) -> dict:
+    refuse_scoring_only_precision(cfg)
     device = None if cfg.device == "auto" else cfg.device
     ctx = DistContext.from_env(device=device, comm_dtype=cfg.comm_dtype)
     say = log if ctx.is_main else (lambda *a, **k: None)

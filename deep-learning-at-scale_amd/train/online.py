@@ -22,6 +22,7 @@ import time
 
 import torch
 
+from ..config import refuse_scoring_only_precision
 from .trainer import _to_dev, small_steps_path
 
 
@@ -119,6 +120,7 @@ class _ChunkStage:
 
 def fit_online(trainer, train, val):
     cfg, ctx, eng = trainer.cfg, trainer.ctx, trainer.eng
+    refuse_scoring_only_precision(cfg)
     Xtr, Ytr = train
     chunk = max(cfg.online_chunk, ctx.world_size)
     passes = max(1, cfg.epochs)

@@ -193,6 +193,114 @@ def bench_wide_forward(rows, rounds, widths=(72, 128, 256, 512), launches=5):
     return out
 
 
+def _spread(v, scale=1e3):
+    return {"median": _median(v) * scale, "min": min(v) * scale, "max": max(v) * scale}
+
+
+def bench_f32(rows, rounds, tmp, widths=(16, 72, 128, 512)):
+    """One scoring pass (``MlpPass.score()``, resident raw columns: assembly + forward) over ``rows``
+    in-memory rows on three routes, windows interleaved: ``bf16`` (device assembly + the bf16 fused
+    forwards), ``fp32-native`` (fp32 device assembly + csrc/mlp_f32.hip) and ``fp32`` (the PyTorch
+    oracle: host assembly, upload, torch). Then the forward alone over the same device-assembled
+    fp32 rows: ``NativeMLP.forward_f32`` against torch's fp32 forward of the same weights on the
+    device. Times in ms: median, min, max over the rounds."""
+    from wellflow.models.mlp import MLPRegressor
+    from wellflow.scoring import MlpPass
+
+    out = {}
+    for Fp in widths:
+        L, Q = Fp - 8, 8  # one categorical column of L labels + 8 continuous ones: F = Fp
+        rng = np.random.default_rng(Fp)
+        names = ["c0"] + [f"x{i}" for i in range(Q)] + ["y"]
+        schema = parse_schema(",".join(names), ",".join(["string"] + ["float"] * (Q + 1)))
+        pool = np.asarray([f"l{k:03d}" for k in range(L)], dtype=object)
+        table = {"c0": pool[rng.integers(0, L, rows)]}
+        for c in names[1:]:
+            table[c] = rng.normal(size=rows).astype(np.float32)
+        pipe = FeaturePipeline(schema, "y", standardize_target=True).fit(take(table, np.arange(0, rows, 16)))
+        torch.manual_seed(0)
+        ref = MLPRegressor(pipe.n_features, (256, 256))
+        routes = ("bf16", "fp32-native", "fp32")
+        ps = {r: MlpPass(_predictor(tmp, "mlp", ref, pipe, schema, precision=r), table, resident=True) for r in routes}
+        with torch.no_grad():
+            y = {r: torch.as_tensor(ps[r].score()).float().cpu().clone() for r in routes}  # warm-up, and the outputs
+            t = {r: [] for r in routes}
+            for _ in range(rounds):
+                for r in routes:
+                    t[r].append(_clock(ps[r].score)[0])
+            # the forward alone, over the fp32 rows the device assembly wrote
+            pn = ps["fp32-native"]
+            X = pn.assemble(*pn.pieces[0])
+            net = ref.to(X.device)
+            fwd = {"fp32-native": lambda: pn.forward(X, 0), "torch_fp32": lambda: net(X)}
+            ydev = net(X).cpu()
+            tk = {k: [] for k in fwd}
+            for _ in range(rounds):
+                for k, fn in fwd.items():
+                    tk[k].append(_events(fn, 3))
+        rec = {"rows": rows, "features": pipe.n_features, "engine_batch": ps["bf16"].B,
+               "pass_ms": {r: _spread(t[r]) for r in routes}, "forward_ms": {k: _spread(v) for k, v in tk.items()},
+               "fp32_over_fp32_native_pass": _median(t["fp32"]) / _median(t["fp32-native"]),
+               "torch_over_kernel_forward": _median(tk["torch_fp32"]) / _median(tk["fp32-native"]),
+               "max_abs_diff_vs_fp32": {r: (y[r] - y["fp32"]).abs().max().item() for r in routes[:2]},
+               "max_abs_diff_kernel_vs_torch_on_device": (y["fp32-native"][: len(ydev)] - ydev).abs().max().item(),
+               "pred_abs_max": y["fp32"].abs().max().item()}
+        out[f"Fp{Fp}"] = rec
+        print(json.dumps({f"Fp{Fp}": rec}), flush=True)
+        del ps, X, net, table, y
+        torch.cuda.empty_cache()
+    return out
+
+
+def f32_job_accuracy(tmp):
+    """What of the bf16 route's documented distance to the fp32 oracle is left in ``fp32-native``, on
+    the fitted MLP of the set-point and interval job tests (18 -> 256 -> 256 -> 1, 200 Adam steps on
+    8 wells x 125 rows): set-point statuses of 1000 rows that differ, and the worst relative
+    difference of the 27 calibration quantiles (3 levels x 8 wells + overall)."""
+    from wellflow.interval import ConformalBands
+    from wellflow.models.mlp import MLPRegressor
+    from wellflow.predict import Predictor
+    from wellflow.setpoint import SetPoint
+
+    schema = parse_schema(NAMES, TYPES)
+    table = load_table("synth", schema, synth_wells=8, synth_steps=125, seed=3)
+    pipe = FeaturePipeline(schema, "flow", standardize_target=True).fit(table)
+    torch.manual_seed(0)
+    ref = MLPRegressor(pipe.n_features, (256, 256))
+    X = torch.from_numpy(pipe.features(table))
+    y = torch.from_numpy(np.asarray(pipe.target_values(table), np.float32)).reshape(-1)
+    opt = torch.optim.Adam(ref.parameters(), lr=2e-3)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        for _ in range(200):
+            opt.zero_grad()
+            ((ref(X).reshape(-1) - y) ** 2).mean().backward()
+            opt.step()
+    finally:
+        torch.set_num_threads(threads)
+    _predictor(tmp, "mlp", ref, pipe, schema)  # saves <tmp>/models/mlp.mdl
+    path = os.path.join(tmp, "models", "mlp.mdl")
+    want, alphas = np.asarray(table["flow"], np.float32), ("0.1", "0.05", "0.5")
+
+    def run(device, precision):
+        sp = SetPoint(Predictor.load(path, schema, device=device, precision=precision, batch=512), points=9,
+                      refine=6).run(table, "choke", want)
+        cb = ConformalBands(Predictor.load(path, schema, device=device, precision=precision, batch=512), alphas=alphas,
+                            by="well").calibrate(table)
+        return sp["bracket"], np.asarray([r["quantile"] for r in cb["rows"]])
+
+    b0, q0 = run("cpu", "fp32")
+    out = {}
+    for precision in ("bf16", "fp32-native"):
+        b, q = run("cuda", precision)
+        rel = np.abs(q - q0) / q0
+        out[precision] = {"setpoint_status_differs_of_1000": int((np.asarray(b) != np.asarray(b0)).sum()),
+                          "quantiles": len(rel), "quantile_rel_max": float(rel.max()),
+                          "quantile_rel_median": float(np.median(rel))}
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rows", type=int, default=2_097_152)
@@ -201,13 +309,20 @@ def main() -> int:
     ap.add_argument("--skip-lstm", action="store_true")
     ap.add_argument("--wide-forward", action="store_true",
                     help="only the MLP forward at Fp = 72, 128, 256, 512: fused wide kernel vs per-layer route")
+    ap.add_argument("--f32", action="store_true",
+                    help="only one scoring pass at Fp = 16, 72, 128, 512 on three routes: bf16, fp32-native (the fp32 "
+                         "kernel) and fp32 (the PyTorch oracle); and the fp32 kernel alone against torch on the device")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("predict_throughput: needs a GPU (no rate is reported without one)", file=sys.stderr)
         return 2
     rec = {"device": torch.cuda.get_device_name(0)}
     with tempfile.TemporaryDirectory() as tmp:
-        if args.wide_forward:
+        if args.f32:
+            rec["mlp_f32_jobs_vs_fp32_oracle"] = f32_job_accuracy(tmp)
+            print(json.dumps(rec), flush=True)
+            rec["mlp_f32"] = bench_f32(args.rows, args.rounds, tmp)
+        elif args.wide_forward:
             rec["mlp_wide_forward"] = bench_wide_forward(args.rows, args.rounds)
         else:
             rec["mlp"], (pipe, table) = bench_mlp(args.rows, args.rounds, tmp)

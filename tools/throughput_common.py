@@ -36,10 +36,10 @@ def _events(fn, launches=10):
     return e0.elapsed_time(e1) / launches * 1e-3
 
 
-def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0):
+def _predictor(tmp, name, ref, pipe, schema, job=None, batch=0, precision="bf16"):
     p = os.path.join(tmp, "models", f"{name}.mdl")
     extra = {"features": pipe.state()}
     if job:
         extra["job"] = job
     save_mdl(p, name, registry.keras_layers(name, ref), extra)
-    return Predictor.load(p, schema, device="cuda", precision="bf16", batch=batch)
+    return Predictor.load(p, schema, device="cuda", precision=precision, batch=batch)
