@@ -49,6 +49,7 @@ _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
     "mlp_wide.hip": _NO_PACKED_F32,
     "mlp_f32.hip": _NO_PACKED_F32,  # the same contract, in fp32 end to end
+    "mlp_f32_grad.hip": _NO_PACKED_F32,  # and for the input gradient built on it
 }
 
 

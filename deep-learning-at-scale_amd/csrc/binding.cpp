@@ -885,6 +885,46 @@ void mlp2_forward_f32(const at::Tensor& X, int64_t ldx, int64_t F, const at::Ten
               "mlp2_forward_f32: the launcher refused the shape");
 }
 
+// Fused fp32 MLP input gradient (mlp_f32_grad.hip): operands as mlp2_forward_f32, plus dX [>= B][ldg]
+// fp32 (ldg >= F, rows 4-B aligned); writes pred[0 .. B) and dX[row][0 .. F) for row < B and nothing
+// else. Every operand and shape the kernel does not take is refused here, by name, before any launch.
+void mlp2_forward_grad_f32(const at::Tensor& X, int64_t ldx, int64_t F, const at::Tensor& W1, const at::Tensor& b1,
+                           const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3,
+                           const at::Tensor& pred, const at::Tensor& dX, int64_t ldg, int64_t B) {
+  constexpr int64_t H = 256;
+  const char* fn = "mlp2_forward_grad_f32: ";
+  const int64_t Fp = (F + 7) / 8 * 8;
+  TORCH_CHECK(F >= 1 && Fp <= wf::kMlpF32MaxFp, fn, "F = ", F, " features (needs 1 .. ", wf::kMlpF32MaxFp,
+              " after padding to a multiple of 8)");
+  TORCH_CHECK(ldx >= F && ldx <= INT32_MAX, fn, "ldx = ", ldx, " (needs F = ", F, " <= ldx < 2^31)");
+  // the kernel's offsets inside a 64-row tile of dX are 32-bit
+  TORCH_CHECK(ldg >= F && ldg <= (1 << 24), fn, "ldg = ", ldg, " (needs F = ", F, " <= ldg <= 2^24)");
+  TORCH_CHECK(B >= 1 && B <= INT32_MAX - wf::kMlpF32Rows, fn, "B = ", B, " rows");
+  const std::pair<const at::Tensor*, const char*> ops[] = {{&X, "X"},   {&W1, "W1"}, {&b1, "b1"},     {&W2, "W2"}, {&b2, "b2"},
+                                                           {&w3, "w3"}, {&b3, "b3"}, {&pred, "pred"}, {&dX, "dX"}};
+  for (const auto& [t, name] : ops) {
+    TORCH_CHECK(t->defined() && t->is_cuda(), fn, name, " must be a GPU tensor");
+    TORCH_CHECK(t->scalar_type() == at::kFloat, fn, name, " must be fp32, got ", t->scalar_type());
+    TORCH_CHECK(t->is_contiguous(), fn, name, " must be contiguous");
+    TORCH_CHECK(t->device() == X.device(), fn, name, " is on ", t->device(), ", X on ", X.device());
+  }
+  const std::tuple<const at::Tensor*, const char*, int64_t> sizes[] = {
+      {&W1, "W1", H * Fp}, {&b1, "b1", H}, {&W2, "W2", H * H}, {&b2, "b2", H}, {&w3, "w3", H}, {&b3, "b3", 1}};
+  for (const auto& [t, name, n] : sizes) {
+    TORCH_CHECK(t->numel() == n, fn, name, " holds ", t->numel(), " elements, needs ", n);
+    TORCH_CHECK(n == 1 || reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, fn, name, " must be 16-byte aligned");
+  }
+  TORCH_CHECK(X.numel() >= (B - 1) * ldx + F, fn, "X holds ", X.numel(), " elements, ", B, " rows of stride ", ldx,
+              " need ", (B - 1) * ldx + F);
+  TORCH_CHECK(dX.numel() >= (B - 1) * ldg + F, fn, "dX holds ", dX.numel(), " elements, ", B, " rows of stride ", ldg,
+              " need ", (B - 1) * ldg + F);
+  TORCH_CHECK(pred.numel() >= B, fn, "pred holds ", pred.numel(), " elements, needs ", B);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
+  TORCH_CHECK(wf::launch_mlp2_grad_f32(fp(X), (long)ldx, (int)F, fp(W1), fp(b1), fp(W2), fp(b2), fp(w3), fp(b3),
+                                       fp(pred), fp(dX), (long)ldg, (int)B, cur_stream()),
+              fn, "the launcher refused the shape");
+}
+
 // The wide forward as a training step's first launch (mlp_wide.hip mlp2_fwd_wide_train_kernel):
 // writes pred, dy, H1, the H2 ReLU bitmask M2 and, with rows, the gathered batch Xout; adds the
 // loss sum and the head gradients. clip > 0: clipped MAE, else MSE. Refusals as mlp2_forward_wide.
@@ -1774,6 +1814,7 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(mlp2_forward_wide);
   WF_DEF(mlp2_forward_wide_train);
   WF_DEF(mlp2_forward_f32);
+  WF_DEF(mlp2_forward_grad_f32);
   m.attr("MLP_F32_ROWS") = wf::kMlpF32Rows;  // the fp32 forward's row tile
   m.attr("MLP_WIDE_ROWS") = wf::kMlpWideRows;  // the wide forward's row tile
   WF_DEF(mlp2_backward);

@@ -248,6 +248,17 @@ constexpr int kMlpF32MaxFp = 512;  // = ASSEMBLE_MAX_F (features.hip)
 bool launch_mlp2_fwd_f32(const float* X, long ldx, int F, const float* W1, const float* b1, const float* W2,
                          const float* b2, const float* w3, const float* b3, float* pred, int B, hipStream_t s);
 
+// ---- fused fp32 MLP input gradient (mlp_f32_grad.hip): the forward above plus, per row,
+// dX[row][f] = dpred/dx_f = (W1^T (m1 * (W2^T (m2 * w3))))_f with the ReLU masks m = (z > 0), in
+// ONE launch over the same 64-row tile. Operands as launch_mlp2_fwd_f32; dX [B][ldg] fp32 with
+// ldg >= F and rows 4-B aligned only (columns >= F and rows >= B are never written). Writes
+// pred[0 .. B) and dX and nothing else (no atomics, no scratch); a row's result does not depend on
+// B or on its position. Returns false (nothing launched) where launch_mlp2_fwd_f32 does, for
+// ldg < F, ldg > 2^24 (offsets inside a tile of dX are 32-bit) and for a null or misaligned dX.
+bool launch_mlp2_grad_f32(const float* X, long ldx, int F, const float* W1, const float* b1, const float* W2,
+                          const float* b2, const float* w3, const float* b3, float* pred, float* dX, long ldg, int B,
+                          hipStream_t s);
+
 // ---- fused MLP backward (mlp_fused.hip), everything but the dW2 GEMM: from H1, H2
 // ([B][256] bf16), dy, w3 / W2 and X: dZ2 ([B][256] bf16, dW2's operand), db1, db2, dw3, db3
 // and — when dW1 != nullptr — dW1 ([256][Fp], Fp <= 32) (fp32, accumulated with atomics);

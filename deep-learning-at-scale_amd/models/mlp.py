@@ -449,27 +449,55 @@ class NativeMLP(Engine):
             return f"{self.Fp} padded input features > 512"
         return None
 
+    def _f32_rows(self, fn: str, X: torch.Tensor) -> tuple:
+        """(b, ldx) of the fp32 rows ``X``, or the refusal of :meth:`forward_f32` and
+        :meth:`input_gradients_f32`, which share their argument checks."""
+        why = self.f32_reason()
+        if why is not None:
+            raise ValueError(f"NativeMLP.{fn}: {why}")
+        if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype == torch.float32 and X.is_contiguous()):
+            raise ValueError(f"NativeMLP.{fn}: X must be a contiguous fp32 [b][ldx] tensor (no copy, no cast "
+                             "is made)")
+        b, ldx = X.shape
+        if X.device != self.params.device:  # (an indexed device, where self.device may be plain "cuda")
+            raise ValueError(f"NativeMLP.{fn}: X is on {X.device}, the engine on {self.params.device}")
+        if not 1 <= b <= self.B:
+            raise ValueError(f"NativeMLP.{fn}: {b} rows (the engine's batch holds 1 .. {self.B})")
+        if ldx < self.F:
+            raise ValueError(f"NativeMLP.{fn}: rows of {ldx} values < {self.F} features")
+        return b, ldx
+
     def forward_f32(self, X: torch.Tensor) -> torch.Tensor:
         """Scoring forward in fp32 end to end, ONE launch (csrc/mlp_f32.hip): ``X`` is an fp32
         ``[b][ldx]`` device tensor (``ldx >= F``; what the fp32 device assembly writes) read in
         place, the weights are the fp32 master copy ``params`` (never the bf16 shadow). Only
         ``pred[:b]`` is written: no training buffer is touched and H1, H2 never reach HBM."""
-        why = self.f32_reason()
-        if why is not None:
-            raise ValueError(f"NativeMLP.forward_f32: {why}")
-        if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype == torch.float32 and X.is_contiguous()):
-            raise ValueError("NativeMLP.forward_f32: X must be a contiguous fp32 [b][ldx] tensor (no copy, no cast "
-                             "is made)")
-        b, ldx = X.shape
-        if X.device != self.params.device:  # (an indexed device, where self.device may be plain "cuda")
-            raise ValueError(f"NativeMLP.forward_f32: X is on {X.device}, the engine on {self.params.device}")
-        if not 1 <= b <= self.B:
-            raise ValueError(f"NativeMLP.forward_f32: {b} rows (the engine's batch holds 1 .. {self.B})")
-        if ldx < self.F:
-            raise ValueError(f"NativeMLP.forward_f32: rows of {ldx} values < {self.F} features")
+        b, ldx = self._f32_rows("forward_f32", X)
         pl, hw, hb = self.lay.views(self.params)
         self._C.mlp2_forward_f32(X, ldx, self.F, pl[0][0], pl[0][1], pl[1][0], pl[1][1], hw, hb, self.pred, b)
         return self.pred[:b]
+
+    def input_gradients_f32(self, X: torch.Tensor, out: torch.Tensor | None = None) -> tuple:
+        """``(pred[:b], dX[:b])``: the fp32 forward of :meth:`forward_f32` and, per row, the gradient
+        of the prediction with respect to the row's ``F`` inputs, ONE launch (csrc/mlp_f32_grad.hip).
+        ``X`` as for :meth:`forward_f32`; ``out``: a contiguous fp32 ``[>= b][ldg >= F]`` tensor on
+        the engine's device (allocated ``[b][F]`` when None), of which only ``[:b, :F]`` is
+        written. The ReLU derivative at 0 is 0. Reads the fp32 master ``params``; no training
+        buffer is touched."""
+        fn = "input_gradients_f32"
+        b, ldx = self._f32_rows(fn, X)
+        if out is None:
+            out = torch.empty((b, self.F), dtype=torch.float32, device=X.device)
+        if not (torch.is_tensor(out) and out.dim() == 2 and out.dtype == torch.float32 and out.is_contiguous()):
+            raise ValueError(f"NativeMLP.{fn}: out must be a contiguous fp32 [rows][ldg] tensor")
+        if out.device != self.params.device:
+            raise ValueError(f"NativeMLP.{fn}: out is on {out.device}, the engine on {self.params.device}")
+        if out.shape[0] < b or out.shape[1] < self.F:
+            raise ValueError(f"NativeMLP.{fn}: out is {tuple(out.shape)}, needs >= {b} rows of >= {self.F} values")
+        pl, hw, hb = self.lay.views(self.params)
+        self._C.mlp2_forward_grad_f32(X, ldx, self.F, pl[0][0], pl[0][1], pl[1][0], pl[1][1], hw, hb, self.pred, out,
+                                      out.shape[1], b)
+        return self.pred[:b], out[:b]
 
     def _recompute_ok(self, B: int) -> bool:
         """The H1-free training step: fused forward writes only the H2 bitmask, the fused

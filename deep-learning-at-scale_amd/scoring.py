@@ -233,6 +233,26 @@ class MlpPass(_Pass):
         for c in range(0, m, B):  # [chunk][Fp] slices read in place; the last one may be short
             self.p[a + c : a + min(c + B, m)].copy_(fwd(X[c : c + B]))
 
+    def gradients(self, cols) -> torch.Tensor:
+        """One pass over the table as it is, through :meth:`NativeMLP.input_gradients_f32`
+        (csrc/mlp_f32_grad.hip; an fp32-native pass only): the network outputs land in ``p`` and
+        the derivative of every row's output with respect to the feature columns ``cols`` comes
+        back as a device fp32 ``[K][n]``. The kernel writes whole ``[chunk][n_features]`` rows
+        into ONE chunk-sized buffer; only the picked columns are kept."""
+        if not (self.native and self.f32):
+            raise ValueError("MlpPass.gradients: the gradient kernel serves the fp32-native pass only")
+        B, cols = self.B, torch.as_tensor(list(cols), dtype=torch.int64, device=self.p.device)
+        G = torch.empty((len(cols), self.M), device=self.p.device)
+        dX = torch.empty((min(B, self.M), self.pred.n_features), device=self.p.device)
+        host = None if self.on_device else self._features()
+        for a, b in self.pieces:
+            X = self.assemble(a, b, None, host)
+            for c in range(0, b - a, B):  # as forward: [chunk][n_features] slices read in place
+                p, g = self.eng.input_gradients_f32(X[c : c + B], dX)
+                self.p[a + c : a + c + len(p)].copy_(p)
+                G[:, a + c : a + c + len(p)].copy_(g[:, cols].t())
+        return G
+
     def _score_host(self, X: np.ndarray) -> np.ndarray:
         X, B = torch.from_numpy(X), self.B
         p = np.empty(self.M, np.float32)

@@ -21,6 +21,10 @@ units that, added to a base value, give the prediction (wellflow/explain.py).
 searches, row by row, the value of one continuous input column at which the model predicts the wanted
 value (``--want-column COL``: one wanted value per row): the inverse of predict (wellflow/setpoint.py).
 
+``python -m wellflow.submit sensitivity <model> columnNames columnTypes targetColumn storagePath dataPath [--columns a,b,..]``
+writes, per row and continuous input column, the derivative of the prediction (raw target units per raw column
+unit) and the elasticity, from the fused fp32 gradient kernel on a GPU (wellflow/sensitivity.py).
+
 ``python -m wellflow.submit interval <model> columnNames columnTypes targetColumn storagePath dataPath [--calibrate]``
 puts a band around every prediction: ``--calibrate`` scores held-out rows and writes, per ``--by`` group and
 level ``--alpha``, the conformal quantile of the residuals; without it the bands are read back and written next
@@ -56,6 +60,10 @@ def main(argv=None) -> int:
         from .setpoint import main as setpoint_main
 
         return setpoint_main(argv[1:])
+    if argv[0] == "sensitivity":  # per-row input gradients and elasticities of a saved .mdl
+        from .sensitivity import main as sensitivity_main
+
+        return sensitivity_main(argv[1:])
     if argv[0] == "interval":  # conformal prediction bands: calibrate on held-out rows, then apply next to the predictions
         from .interval import main as interval_main
 
