@@ -50,6 +50,7 @@ SOURCE_FLAGS = {
     "mlp_wide.hip": _NO_PACKED_F32,
     "mlp_f32.hip": _NO_PACKED_F32,  # the same contract, in fp32 end to end
     "mlp_f32_grad.hip": _NO_PACKED_F32,  # and for the input gradient built on it
+    "mlp_f32_path.hip": _NO_PACKED_F32,  # and for its average along a path (integrated gradients)
 }
 
 

@@ -925,6 +925,89 @@ void mlp2_forward_grad_f32(const at::Tensor& X, int64_t ldx, int64_t F, const at
               fn, "the launcher refused the shape");
 }
 
+// Fused fp32 MLP path-averaged input gradient (mlp_f32_path.hip): operands and checks as
+// mlp2_forward_grad_f32 without b3 and pred, plus the baseline row xb (contiguous fp32, >= F values, X's
+// device) and 1 <= steps <= 1024; writes avg[row][0 .. F) for row < B and nothing else.
+void mlp2_path_grad_f32(const at::Tensor& X, int64_t ldx, int64_t F, const at::Tensor& xb, const at::Tensor& W1,
+                        const at::Tensor& b1, const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& w3,
+                        int64_t steps, const at::Tensor& avg, int64_t ldg, int64_t B) {
+  constexpr int64_t H = 256;
+  const char* fn = "mlp2_path_grad_f32: ";
+  const int64_t Fp = (F + 7) / 8 * 8;
+  TORCH_CHECK(F >= 1 && Fp <= wf::kMlpF32MaxFp, fn, "F = ", F, " features (needs 1 .. ", wf::kMlpF32MaxFp,
+              " after padding to a multiple of 8)");
+  TORCH_CHECK(steps >= 1 && steps <= wf::kMlpPathMaxSteps, fn, "steps = ", steps, " (needs 1 .. ",
+              wf::kMlpPathMaxSteps, ")");
+  TORCH_CHECK(ldx >= F && ldx <= INT32_MAX, fn, "ldx = ", ldx, " (needs F = ", F, " <= ldx < 2^31)");
+  // the kernel's offsets inside a 64-row tile of avg are 32-bit
+  TORCH_CHECK(ldg >= F && ldg <= (1 << 24), fn, "ldg = ", ldg, " (needs F = ", F, " <= ldg <= 2^24)");
+  TORCH_CHECK(B >= 1 && B <= INT32_MAX - wf::kMlpF32Rows, fn, "B = ", B, " rows");
+  const std::pair<const at::Tensor*, const char*> ops[] = {{&X, "X"},   {&xb, "xb"}, {&W1, "W1"}, {&b1, "b1"},
+                                                           {&W2, "W2"}, {&b2, "b2"}, {&w3, "w3"}, {&avg, "avg"}};
+  for (const auto& [t, name] : ops) {
+    TORCH_CHECK(t->defined() && t->is_cuda(), fn, name, " must be a GPU tensor");
+    TORCH_CHECK(t->scalar_type() == at::kFloat, fn, name, " must be fp32, got ", t->scalar_type());
+    TORCH_CHECK(t->is_contiguous(), fn, name, " must be contiguous");
+    TORCH_CHECK(t->device() == X.device(), fn, name, " is on ", t->device(), ", X on ", X.device());
+  }
+  const std::tuple<const at::Tensor*, const char*, int64_t> sizes[] = {
+      {&W1, "W1", H * Fp}, {&b1, "b1", H}, {&W2, "W2", H * H}, {&b2, "b2", H}, {&w3, "w3", H}};
+  for (const auto& [t, name, n] : sizes) {
+    TORCH_CHECK(t->numel() == n, fn, name, " holds ", t->numel(), " elements, needs ", n);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, fn, name, " must be 16-byte aligned");
+  }
+  TORCH_CHECK(xb.numel() >= F, fn, "xb holds ", xb.numel(), " elements, the baseline row needs ", F);
+  TORCH_CHECK(X.numel() >= (B - 1) * ldx + F, fn, "X holds ", X.numel(), " elements, ", B, " rows of stride ", ldx,
+              " need ", (B - 1) * ldx + F);
+  TORCH_CHECK(avg.numel() >= (B - 1) * ldg + F, fn, "avg holds ", avg.numel(), " elements, ", B, " rows of stride ",
+              ldg, " need ", (B - 1) * ldg + F);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
+  TORCH_CHECK(wf::launch_mlp2_path_grad_f32(fp(X), (long)ldx, (int)F, fp(xb), fp(W1), fp(b1), fp(W2), fp(b2), fp(w3),
+                                            (int)steps, fp(avg), (long)ldg, (int)B, cur_stream()),
+              fn, "the launcher refused the shape");
+}
+
+// Column contributions of a path attribution (score.hip path_attr_kernel): X [M][ldx], avg [M][lda]
+// fp32 (2-D, contiguous, >= F values per row), xb fp32 [>= F], off / size int32 [K] with every span
+// inside [0, F); phi contiguous fp64 [K][N], of which cells [k][row0 .. row0 + M) are written:
+// the uncontracted fp64 sum over the span of (X - xb) * avg in ascending f. Stream-ordered.
+void path_attr(const at::Tensor& X, const at::Tensor& avg, const at::Tensor& xb, int64_t F, const at::Tensor& off,
+               const at::Tensor& size, const at::Tensor& phi, int64_t row0) {
+  const char* fn = "path_attr: ";
+  for (const at::Tensor* t : {&X, &avg}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2,
+                fn, "X / avg must be contiguous fp32 [M][ld] GPU tensors");
+    TORCH_CHECK(F >= 1 && t->size(1) >= F, fn, "rows of ", t->size(1), " values < F = ", F);
+  }
+  const int64_t M = X.size(0);
+  TORCH_CHECK(M >= 1 && avg.size(0) == M, fn, "X holds ", M, " rows, avg ", avg.size(0), " (need the same, >= 1)");
+  TORCH_CHECK(xb.defined() && xb.is_cuda() && xb.scalar_type() == at::kFloat && xb.is_contiguous() && xb.numel() >= F,
+              fn, "xb must be a contiguous fp32 GPU tensor of >= ", F, " values");
+  for (const at::Tensor* t : {&off, &size}) {
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous() && t->dim() == 1,
+                fn, "off / size must be contiguous int32 GPU vectors");
+  }
+  const int64_t K = off.numel();
+  TORCH_CHECK(K >= 1 && K <= INT32_MAX && size.numel() == K, fn, "off holds ", K, " spans, size ", size.numel());
+  TORCH_CHECK(phi.defined() && phi.is_cuda() && phi.scalar_type() == at::kDouble && phi.is_contiguous() &&
+                  phi.dim() == 2 && phi.size(0) == K,
+              fn, "phi must be a contiguous fp64 [", K, "][N] GPU tensor");
+  TORCH_CHECK(row0 >= 0 && row0 + M <= phi.size(1), fn, "rows ", row0, " .. ", row0 + M, " outside phi's ", phi.size(1));
+  for (const at::Tensor* t : {&avg, &xb, &off, &size, &phi})
+    TORCH_CHECK(t->device() == X.device(), fn, "tensors on different devices");
+  // every span is checked against [0, F) before any launch, on a host copy of the two small vectors
+  // (one stream sync per call; the kernel relies on this check and makes none of its own)
+  const at::Tensor o = off.cpu(), z = size.cpu();
+  for (int64_t k = 0; k < K; ++k) {
+    const int64_t a = o.data_ptr<int>()[k], n = z.data_ptr<int>()[k];
+    TORCH_CHECK(a >= 0 && n >= 0 && a + n <= F, fn, "span ", k, " = [", a, ", ", a + n, ") outside [0, ", F, ")");
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
+  wf::launch_path_attr(X.data_ptr<float>(), (long)X.size(1), avg.data_ptr<float>(), (long)avg.size(1),
+                       xb.data_ptr<float>(), (int)F, off.data_ptr<int>(), size.data_ptr<int>(), (int)K, (long)M,
+                       phi.data_ptr<double>() + row0, (long)phi.size(1), cur_stream());
+}
+
 // The wide forward as a training step's first launch (mlp_wide.hip mlp2_fwd_wide_train_kernel):
 // writes pred, dy, H1, the H2 ReLU bitmask M2 and, with rows, the gathered batch Xout; adds the
 // loss sum and the head gradients. clip > 0: clipped MAE, else MSE. Refusals as mlp2_forward_wide.
@@ -1815,6 +1898,8 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(mlp2_forward_wide_train);
   WF_DEF(mlp2_forward_f32);
   WF_DEF(mlp2_forward_grad_f32);
+  WF_DEF(mlp2_path_grad_f32);
+  WF_DEF(path_attr);
   m.attr("MLP_F32_ROWS") = wf::kMlpF32Rows;  // the fp32 forward's row tile
   m.attr("MLP_WIDE_ROWS") = wf::kMlpWideRows;  // the wide forward's row tile
   WF_DEF(mlp2_backward);

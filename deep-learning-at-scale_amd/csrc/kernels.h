@@ -259,6 +259,19 @@ bool launch_mlp2_grad_f32(const float* X, long ldx, int F, const float* W1, cons
                           const float* b2, const float* w3, const float* b3, float* pred, float* dX, long ldg, int B,
                           hipStream_t s);
 
+// ---- fused fp32 MLP path-averaged input gradient (mlp_f32_path.hip; integrated gradients):
+// avg[row][f] = (1/steps) sum_j df/dx_f (xb + alpha_j (x_row - xb)), alpha_j = (float)(2j + 1) /
+// (float)(2 steps) (correctly rounded fp32 division), for ONE baseline row xb [F] fp32 shared by
+// all rows. Layer 1 and dX = G1 x W1 run once per 64-row tile, the two 256 x 256 products once
+// per step, all on chip. X, W1 .. w3, ldg and B as launch_mlp2_grad_f32; writes avg[row][0 .. F)
+// for row < B and nothing else (no prediction, no atomics, no scratch); a row's result does not
+// depend on B or on its position. Returns false (nothing launched) where launch_mlp2_grad_f32
+// does, for steps outside 1 .. kMlpPathMaxSteps and for a null or misaligned xb.
+constexpr int kMlpPathMaxSteps = 1024;
+bool launch_mlp2_path_grad_f32(const float* X, long ldx, int F, const float* xb, const float* W1, const float* b1,
+                               const float* W2, const float* b2, const float* w3, int steps, float* avg, long ldg,
+                               int B, hipStream_t s);
+
 // ---- fused MLP backward (mlp_fused.hip), everything but the dW2 GEMM: from H1, H2
 // ([B][256] bf16), dy, w3 / W2 and X: dZ2 ([B][256] bf16, dW2's operand), db1, db2, dw3, db3
 // and — when dW1 != nullptr — dW1 ([256][Fp], Fp <= 32) (fp32, accumulated with atomics);
@@ -507,6 +520,16 @@ void launch_err_sums(const float* pred, const float* y, long M, double y_scale, 
 // p_cur and p_prev must not overlap.
 void launch_attr_step(const float* p_cur, float* p_prev, long M, double y_scale, double y_shift, double* acc,
                       double* sq, bool start, hipStream_t s);
+
+// ---- per-row column contributions of a path attribution (score.hip) ----
+// phi[k * ldp + i] = sum_{f = off[k] .. off[k] + size[k] - 1} ((double)X[i][f] - (double)xb[f]) *
+// (double)avg[i][f] for i < M, k < K: fp64, never contracted, the sum started at 0.0 and taken in
+// ascending f; a span of size 0 gives exactly 0.0. X [M][ldx], avg [M][lda] fp32, xb [F] fp32, off /
+// size int32 [K] with 0 <= off, 0 <= size, off + size <= F (the caller checks). phi points at the
+// first row's cell of a [K][ldp] fp64 table, so pieces fill one table. Cell (k, i) is written by
+// ONE thread: bitwise equal to the numpy rule (integrated.path_attr_host).
+void launch_path_attr(const float* X, long ldx, const float* avg, long lda, const float* xb, int F, const int* off,
+                      const int* size, int K, long M, double* phi, long ldp, hipStream_t s);
 
 // ---- grouped prediction sums (score.hip) ----
 // v = (double)pred * y_scale + y_shift; out [G][3] = {n_g, sum v, sum v * v} per group, fp64, from a

@@ -170,6 +170,80 @@ void launch_attr_step(const float* p_cur, float* p_prev, long M, double y_scale,
                      sq, start ? 1 : 0);
 }
 
+// ---- per-row column contributions of a path attribution (wellflow/integrated.py) ----
+//
+// Integrated gradients end in phi[k][i] = sum over the features f of column k's span of
+// (x[i][f] - x'[f]) * avg[i][f], avg from mlp_f32_path.hip. The difference, the product and the sum
+// are correctly rounded fp64 operations, never fused; the sum starts at 0.0 and runs in ascending
+// f, so the table equals the numpy rule (path_attr_host) bit for bit, and a span of size 0 gives
+// exactly 0.0. A NaN in avg reaches the cells of its own row and span only.
+//
+// One workgroup of 256 threads per 64-row tile, grid-stride; the features go by in chunks of 32.
+// Load phase: lane = feature, so X and avg are read in 128-B row segments; the fp64 products land
+// in an LDS tile [64][32 + 1]. Sum phase: thread = (row, k mod 4) walks the spans that meet the
+// chunk and adds its row's products in ascending f; a span that began in an earlier chunk carries
+// its sum in its own phi cell, which only this thread reads and writes.
+namespace {
+
+constexpr int PA_ROWS = 64, PA_CHUNK = 32;
+
+__device__ __forceinline__ double path_term(float x, float xb, float a) {
+#pragma clang fp contract(off)
+  const double d = (double)x - (double)xb;
+  return d * (double)a;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void path_attr_kernel(const float* __restrict__ X, long ldx,
+                                                        const float* __restrict__ avg, long lda,
+                                                        const float* __restrict__ xb, int F,
+                                                        const int* __restrict__ off, const int* __restrict__ size, int K,
+                                                        long M, double* phi, long ldp) {
+#pragma clang fp contract(off)
+  __shared__ double prod[PA_ROWS][PA_CHUNK + 1];
+  const int lf = threadIdx.x & 31, lr = threadIdx.x >> 5;   // load phase: feature, row (+ 8 j)
+  const int row = threadIdx.x & 63, kq = threadIdx.x >> 6;  // sum phase
+  const long ntiles = (M + PA_ROWS - 1) / PA_ROWS;
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long r0 = tile * PA_ROWS;
+    for (int c0 = 0; c0 < F; c0 += PA_CHUNK) {
+      __syncthreads();  // every read of the previous chunk's products is done
+      const int f = c0 + lf;
+      const float b = f < F ? xb[f] : 0.f;
+#pragma unroll
+      for (int j = 0; j < PA_ROWS / 8; ++j) {
+        const long r = r0 + lr + 8 * j;
+        prod[lr + 8 * j][lf] = (r < M && f < F) ? path_term(X[r * ldx + f], b, avg[r * lda + f]) : 0.0;
+      }
+      __syncthreads();
+      if (r0 + row < M) {
+        for (int k = kq; k < K; k += 4) {
+          const int o = off[k], e = o + size[k];
+          const int lo = o > c0 ? o : c0, hi = e < c0 + PA_CHUNK ? e : c0 + PA_CHUNK;
+          double* cell = phi + (long)k * ldp + r0 + row;
+          if (lo < hi) {
+            double s = lo == o ? 0.0 : *cell;
+            for (int ff = lo; ff < hi; ++ff) s = s + prod[row][ff - c0];
+            *cell = s;
+          } else if (o == e && c0 == 0) {
+            *cell = 0.0;
+          }
+        }
+      }
+    }
+  }
+}
+
+void launch_path_attr(const float* X, long ldx, const float* avg, long lda, const float* xb, int F, const int* off,
+                      const int* size, int K, long M, double* phi, long ldp, hipStream_t s) {
+  long blocks = (M + PA_ROWS - 1) / PA_ROWS;  // capped grid, grid-stride over the rest
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(path_attr_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X, ldx, avg, lda, xb, F, off, size, K, M,
+                     phi, ldp);
+}
+
 // ---- grouped prediction sums (response curves, wellflow/response.py) ----
 //
 // A response-curve run scores the table 1 + sum(grid sizes) times and wants, per pass, the mean

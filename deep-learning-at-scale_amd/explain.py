@@ -3,6 +3,7 @@
     python -m wellflow.explain <model> columnNames columnTypes targetColumn storagePath dataPath
                                [--repeats R=8] [--columns a,b,..] [--std] [--out PATH] [--seed S] [--device D]
                                [--precision P] [--seq-len T] [--group-col COL] [--batch-size B] [--header]
+                               [--method shapley|ig] (ig: [--steps M=32] [--baseline mean|N]; wellflow/integrated.py)
 
 The prediction, importance and response jobs answer global questions. This one is local: per row
 and per input column a contribution ``phi`` in raw target units which, added to a base value,
@@ -229,13 +230,30 @@ def _write_csv(path: str, table: dict, names: list, result: dict, with_std: bool
 
 
 def run_explain(model: str, argv, log=print) -> dict:
+    parser = []
+
     def add_arguments(ap):
+        parser.append(ap)
         ap.add_argument("--repeats", type=int, default=8, help="sampled column orders / background rows per row (default 8)")
         ap.add_argument("--columns", default=None, help="comma-separated input columns to attribute to (default: all)")
         ap.add_argument("--std", action="store_true", help="also write std_<column>: the spread over the repeats")
+        ap.add_argument("--method", choices=("shapley", "ig"), default="shapley",
+                        help="shapley (sampling, default) or ig (integrated gradients, wellflow/integrated.py)")
+        ap.add_argument("--steps", type=int, default=None, help="ig: midpoint steps along the path (default 32)")
+        ap.add_argument("--baseline", default=None, help="ig: 'mean' (the table's mean feature row, default) or a row number")
 
     ns, cfg, schema, out_path, load_predictor, load_data = scoring_job(
         "explain", "attribution", "explain", "dataPath", model, argv, add_arguments)
+    # which of the two methods' own flags were given: a second parse with every default None, so the
+    # parser's own rules (abbreviations, --flag=value) decide, not a scan of the strings
+    own = {"ig": ("steps", "baseline"), "shapley": ("repeats", "std", "seed")}
+    parser[0].set_defaults(**{d: None for ds in own.values() for d in ds})
+    probe = parser[0].parse_args(list(argv))
+    for dest in own["shapley" if ns.method == "ig" else "ig"]:
+        if getattr(probe, dest) is not None:
+            raise ValueError(f"--{dest} does not apply to --method {ns.method}")
+    if ns.method == "ig":
+        return _run_ig(model, ns, cfg, schema, out_path, load_data, log)
     if skipped := other_rank(model, out_path):
         return skipped
     job = ShapleyAttribution(load_predictor(), repeats=ns.repeats, seed=cfg.seed)
@@ -251,6 +269,42 @@ def run_explain(model: str, argv, log=print) -> dict:
     by = sorted(range(len(result["columns"])), key=lambda k: (0, 0.0) if np.isnan(result["mean_abs"][k])
                 else (1, -result["mean_abs"][k]))  # descending; NaN first (shown, not hidden); ties keep the order
     for k in by:
+        log("%s: mean |phi| %f" % (result["columns"][k], result["mean_abs"][k]))
+    return result
+
+
+def _run_ig(model: str, ns, cfg, schema, out_path: str, load_data, log) -> dict:
+    """``--method ig``: integrated gradients (wellflow/integrated.py), through the fused path kernel
+    on a GPU; the model is loaded as the sensitivity job loads it."""
+    from .integrated import IntegratedGradients, _note, refuse_model, write_ig_csv
+    from .sensitivity import native_precision
+
+    refuse_model(model)  # lstm, cnn: before anything is loaded
+    if skipped := other_rank(model, out_path):
+        return skipped
+    batch = cfg.batch_size if ns.batch_size is not None else 0
+    want = native_precision(model, cfg.device, cfg.precision)
+    load = lambda precision: Predictor.load(cfg.mdl_path(model), schema, device=cfg.device, precision=precision,  # noqa: E731
+                                            seq_len=cfg.seq_len, group_col=cfg.group_col, batch=batch)
+    try:
+        pred = load(want)
+        if want == "fp32-native" and cfg.precision != want:
+            _note(f"explain: --precision {cfg.precision} is served in fp32 (fp32-native): there is no bf16 path kernel")
+    except ValueError as e:
+        if want != "fp32-native" or "fp32-native" not in str(e):
+            raise
+        _note(f"explain: {e}")  # the kernel refuses the shape: the oracle serves it
+        pred = load("fp32")
+    job = IntegratedGradients(pred, steps=32 if ns.steps is None else ns.steps,
+                              baseline="mean" if ns.baseline is None else ns.baseline)
+    table = load_data()
+    result = job.run(table, columns=comma_list(ns.columns))
+    result["out"] = out_path
+    write_ig_csv(out_path, table, schema.names, result)
+    log("Rows scored: %d" % result["scored"])
+    log("Mean prediction: %f" % float(np.mean(result["prediction"])))
+    log("Max |residual|: %g" % float(np.max(np.abs(result["residual"]))))
+    for k in np.argsort(-result["mean_abs"], kind="stable"):
         log("%s: mean |phi| %f" % (result["columns"][k], result["mean_abs"][k]))
     return result
 

@@ -486,6 +486,15 @@ class NativeMLP(Engine):
         buffer is touched."""
         fn = "input_gradients_f32"
         b, ldx = self._f32_rows(fn, X)
+        out = self._f32_out(fn, X, b, out)
+        pl, hw, hb = self.lay.views(self.params)
+        self._C.mlp2_forward_grad_f32(X, ldx, self.F, pl[0][0], pl[0][1], pl[1][0], pl[1][1], hw, hb, self.pred, out,
+                                      out.shape[1], b)
+        return self.pred[:b], out[:b]
+
+    def _f32_out(self, fn: str, X: torch.Tensor, b: int, out) -> torch.Tensor:
+        """The ``[>= b][ldg >= F]`` fp32 output rows of the two gradient methods: ``out``, checked, or
+        a new ``[b][F]`` tensor."""
         if out is None:
             out = torch.empty((b, self.F), dtype=torch.float32, device=X.device)
         if not (torch.is_tensor(out) and out.dim() == 2 and out.dtype == torch.float32 and out.is_contiguous()):
@@ -494,10 +503,31 @@ class NativeMLP(Engine):
             raise ValueError(f"NativeMLP.{fn}: out is on {out.device}, the engine on {self.params.device}")
         if out.shape[0] < b or out.shape[1] < self.F:
             raise ValueError(f"NativeMLP.{fn}: out is {tuple(out.shape)}, needs >= {b} rows of >= {self.F} values")
-        pl, hw, hb = self.lay.views(self.params)
-        self._C.mlp2_forward_grad_f32(X, ldx, self.F, pl[0][0], pl[0][1], pl[1][0], pl[1][1], hw, hb, self.pred, out,
-                                      out.shape[1], b)
-        return self.pred[:b], out[:b]
+        return out
+
+    def path_gradients_f32(self, X: torch.Tensor, baseline: torch.Tensor, steps: int,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+        """``avg[:b]``: per row the input gradient of :meth:`input_gradients_f32` averaged over
+        ``steps`` midpoints ``alpha_j = (2j + 1) / (2 steps)`` (fp32) of the straight path from the
+        ONE row ``baseline`` (contiguous fp32, ``>= F`` values, on the engine's device) to the row,
+        ONE launch (csrc/mlp_f32_path.hip): what integrated gradients multiply by ``x - baseline``.
+        ``X`` and ``out`` as for :meth:`input_gradients_f32`; ``1 <= steps <= 1024``. Only
+        ``out[:b, :F]`` is written: no training buffer and not ``pred``."""
+        fn = "path_gradients_f32"
+        b, ldx = self._f32_rows(fn, X)
+        if not (torch.is_tensor(baseline) and baseline.dtype == torch.float32 and baseline.is_contiguous()):
+            raise ValueError(f"NativeMLP.{fn}: baseline must be a contiguous fp32 tensor (one row)")
+        if baseline.device != self.params.device:
+            raise ValueError(f"NativeMLP.{fn}: baseline is on {baseline.device}, the engine on {self.params.device}")
+        if baseline.numel() < self.F:
+            raise ValueError(f"NativeMLP.{fn}: baseline holds {baseline.numel()} values < {self.F} features")
+        if not (isinstance(steps, int) and 1 <= steps <= 1024):
+            raise ValueError(f"NativeMLP.{fn}: steps = {steps!r} (needs an int in 1 .. 1024)")
+        out = self._f32_out(fn, X, b, out)
+        pl, hw, _ = self.lay.views(self.params)
+        self._C.mlp2_path_grad_f32(X, ldx, self.F, baseline, pl[0][0], pl[0][1], pl[1][0], pl[1][1], hw, steps, out,
+                                   out.shape[1], b)
+        return out[:b]
 
     def _recompute_ok(self, B: int) -> bool:
         """The H1-free training step: fused forward writes only the H2 bitmask, the fused

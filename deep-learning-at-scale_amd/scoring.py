@@ -253,6 +253,29 @@ class MlpPass(_Pass):
                 G[:, a + c : a + c + len(p)].copy_(g[:, cols].t())
         return G
 
+    def path_attributions(self, baseline: torch.Tensor, off, size, steps: int) -> torch.Tensor:
+        """Integrated gradients of the table as it is against the ONE feature row ``baseline``
+        (fp32 ``[n_features]`` on the device; an fp32-native pass only): per piece and chunk,
+        assemble, :meth:`NativeMLP.path_gradients_f32` (csrc/mlp_f32_path.hip) into ONE chunk-sized
+        buffer, then ``path_attr`` (csrc/score.hip), which sums ``(x - baseline) * avg`` over the
+        feature span ``[off[k], off[k] + size[k])`` of every column ``k`` in fp64. Returns the
+        device fp64 ``[K][n]`` table; ``p`` is not touched."""
+        if not (self.native and self.f32):
+            raise ValueError("MlpPass.path_attributions: the path kernel serves the fp32-native pass only")
+        from .ops.native import lib
+
+        B, dev, F = self.B, self.p.device, self.pred.n_features
+        off, size = (torch.as_tensor(np.asarray(v, np.int32), device=dev) for v in (off, size))
+        phi = torch.empty((len(off), self.M), dtype=torch.float64, device=dev)
+        avg = torch.empty((min(B, self.M), F), device=dev)
+        host = None if self.on_device else self._features()
+        for a, b in self.pieces:
+            X = self.assemble(a, b, None, host)
+            for c in range(0, b - a, B):  # as forward: [chunk][n_features] slices read in place
+                g = self.eng.path_gradients_f32(X[c : c + B], baseline, steps, avg)
+                lib().path_attr(X[c : c + len(g)], g, baseline, F, off, size, phi, a + c)
+        return phi
+
     def _score_host(self, X: np.ndarray) -> np.ndarray:
         X, B = torch.from_numpy(X), self.B
         p = np.empty(self.M, np.float32)

@@ -21,6 +21,9 @@ units that, added to a base value, give the prediction (wellflow/explain.py).
 searches, row by row, the value of one continuous input column at which the model predicts the wanted
 value (``--want-column COL``: one wanted value per row): the inverse of predict (wellflow/setpoint.py).
 
+``python -m wellflow.submit explain <model> ... --method ig [--steps M] [--baseline mean|N]`` attributes the same
+prediction deterministically with integrated gradients, from the fused fp32 path kernel on a GPU (wellflow/integrated.py).
+
 ``python -m wellflow.submit sensitivity <model> columnNames columnTypes targetColumn storagePath dataPath [--columns a,b,..]``
 writes, per row and continuous input column, the derivative of the prediction (raw target units per raw column
 unit) and the elasticity, from the fused fp32 gradient kernel on a GPU (wellflow/sensitivity.py).
