@@ -51,6 +51,7 @@ SOURCE_FLAGS = {
     "mlp_f32.hip": _NO_PACKED_F32,  # the same contract, in fp32 end to end
     "mlp_f32_grad.hip": _NO_PACKED_F32,  # and for the input gradient built on it
     "mlp_f32_path.hip": _NO_PACKED_F32,  # and for its average along a path (integrated gradients)
+    "mlp_f32_shap.hip": _NO_PACKED_F32,  # and for the coalition sums of the exact Shapley attribution
 }
 
 

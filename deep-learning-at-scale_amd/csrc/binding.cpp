@@ -1008,6 +1008,82 @@ void path_attr(const at::Tensor& X, const at::Tensor& avg, const at::Tensor& xb,
                        phi.data_ptr<double>() + row0, (long)phi.size(1), cur_stream());
 }
 
+// Fused fp32 MLP exact Shapley attribution (mlp_f32_shap.hip): X, xb and the weight views as
+// mlp2_path_grad_f32, plus b3; off / size: HOST int32 [K] feature spans of the picked columns (source
+// order, disjoint, inside [0, F); the launcher checks them), coef: HOST fp64 [2][K + 1]; scratch: fp32
+// on X's device, >= mlp2_shapley_scratch_floats(B, K) values; phi: contiguous fp64 [K][N], cells
+// [c][row0 .. row0 + B) are written; p0, pfull: fp32 [>= B]; p_out: None or contiguous fp32 [2^K][>= B].
+// Nothing else is written. Stream-ordered; nothing is read back here.
+void mlp2_shapley_f32(const at::Tensor& X, int64_t ldx, int64_t F, const at::Tensor& xb, const at::Tensor& W1,
+                      const at::Tensor& b1, const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& w3,
+                      const at::Tensor& b3, const at::Tensor& off, const at::Tensor& size, const at::Tensor& coef,
+                      const at::Tensor& scratch, const at::Tensor& phi, int64_t row0, const at::Tensor& p0,
+                      const at::Tensor& pfull, c10::optional<at::Tensor> p_out, int64_t B) {
+  constexpr int64_t H = 256;
+  const char* fn = "mlp2_shapley_f32: ";
+  const int64_t Fp = (F + 7) / 8 * 8;
+  TORCH_CHECK(F >= 1 && Fp <= wf::kMlpF32MaxFp, fn, "F = ", F, " features (needs 1 .. ", wf::kMlpF32MaxFp,
+              " after padding to a multiple of 8)");
+  TORCH_CHECK(ldx >= F && ldx <= INT32_MAX, fn, "ldx = ", ldx, " (needs F = ", F, " <= ldx < 2^31)");
+  TORCH_CHECK(B >= 1 && B <= INT32_MAX - wf::kMlpF32Rows, fn, "B = ", B, " rows");
+  for (const at::Tensor* t : {&off, &size})
+    TORCH_CHECK(t->defined() && t->is_cpu() && t->scalar_type() == at::kInt && t->is_contiguous() && t->dim() == 1,
+                fn, "off / size must be contiguous int32 CPU vectors");
+  const int64_t K = off.numel();
+  TORCH_CHECK(K >= 1 && K <= wf::kMlpShapMaxCols && size.numel() == K, fn, "off holds ", K, " spans, size ",
+              size.numel(), " (needs the same, 1 .. ", wf::kMlpShapMaxCols, ")");
+  TORCH_CHECK(coef.defined() && coef.is_cpu() && coef.scalar_type() == at::kDouble && coef.is_contiguous() &&
+                  coef.numel() == 2 * (K + 1),
+              fn, "coef must be a contiguous fp64 CPU tensor [2][", K + 1, "]");
+  const std::pair<const at::Tensor*, const char*> ops[] = {
+      {&X, "X"},   {&xb, "xb"}, {&W1, "W1"},           {&b1, "b1"}, {&W2, "W2"},      {&b2, "b2"},
+      {&w3, "w3"}, {&b3, "b3"}, {&scratch, "scratch"}, {&p0, "p0"}, {&pfull, "pfull"}};
+  for (const auto& [t, name] : ops) {
+    TORCH_CHECK(t->defined() && t->is_cuda(), fn, name, " must be a GPU tensor");
+    TORCH_CHECK(t->scalar_type() == at::kFloat, fn, name, " must be fp32, got ", t->scalar_type());
+    TORCH_CHECK(t->is_contiguous(), fn, name, " must be contiguous");
+    TORCH_CHECK(t->device() == X.device(), fn, name, " is on ", t->device(), ", X on ", X.device());
+  }
+  const std::tuple<const at::Tensor*, const char*, int64_t> sizes[] = {
+      {&W1, "W1", H * Fp}, {&b1, "b1", H}, {&W2, "W2", H * H}, {&b2, "b2", H}, {&w3, "w3", H}, {&b3, "b3", 1}};
+  for (const auto& [t, name, n] : sizes) {
+    TORCH_CHECK(t->numel() == n, fn, name, " holds ", t->numel(), " elements, needs ", n);
+    TORCH_CHECK(n == 1 || reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, fn, name, " must be 16-byte aligned");
+  }
+  TORCH_CHECK(xb.numel() >= F, fn, "xb holds ", xb.numel(), " elements, the baseline row needs ", F);
+  TORCH_CHECK(X.numel() >= (B - 1) * ldx + F, fn, "X holds ", X.numel(), " elements, ", B, " rows of stride ", ldx,
+              " need ", (B - 1) * ldx + F);
+  TORCH_CHECK(p0.numel() >= B && pfull.numel() >= B, fn, "p0 / pfull hold ", p0.numel(), " / ", pfull.numel(),
+              " elements, need ", B);
+  TORCH_CHECK(phi.defined() && phi.is_cuda() && phi.scalar_type() == at::kDouble && phi.is_contiguous() &&
+                  phi.dim() == 2 && phi.size(0) == K && phi.device() == X.device(),
+              fn, "phi must be a contiguous fp64 [", K, "][N] tensor on X's device");
+  TORCH_CHECK(row0 >= 0 && row0 + B <= phi.size(1), fn, "rows ", row0, " .. ", row0 + B, " outside phi's ", phi.size(1));
+  float* po = nullptr;
+  int64_t ldp = 0;
+  if (p_out.has_value()) {
+    const at::Tensor& t = *p_out;
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == 2 &&
+                    t.size(0) == (int64_t(1) << K) && t.size(1) >= B && t.device() == X.device(),
+                fn, "p_out must be a contiguous fp32 [", int64_t(1) << K, "][>= ", B, "] tensor on X's device");
+    po = t.data_ptr<float>();
+    ldp = t.size(1);
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
+  const char* why = wf::launch_mlp2_shapley_f32(
+      fp(X), (long)ldx, (int)F, fp(xb), fp(W1), fp(b1), fp(W2), fp(b2), fp(w3), fp(b3), (int)K, off.data_ptr<int>(),
+      size.data_ptr<int>(), coef.data_ptr<double>(), scratch.data_ptr<float>(), (size_t)scratch.numel(),
+      phi.data_ptr<double>() + row0, (long)phi.size(1), p0.data_ptr<float>(), pfull.data_ptr<float>(), po, (long)ldp,
+      (int)B, cur_stream());
+  TORCH_CHECK(why == nullptr, fn, "the launcher refused: ", why);
+}
+
+int64_t mlp2_shapley_scratch_floats(int64_t B, int64_t K) {
+  TORCH_CHECK(B >= 1 && B <= INT32_MAX - wf::kMlpF32Rows && K >= 1 && K <= wf::kMlpShapMaxCols,
+              "mlp2_shapley_scratch_floats: B = ", B, ", K = ", K, " (needs B >= 1, K in 1 .. ", wf::kMlpShapMaxCols, ")");
+  return (int64_t)wf::mlp2_shapley_scratch_floats((int)B, (int)K);
+}
+
 // The wide forward as a training step's first launch (mlp_wide.hip mlp2_fwd_wide_train_kernel):
 // writes pred, dy, H1, the H2 ReLU bitmask M2 and, with rows, the gathered batch Xout; adds the
 // loss sum and the head gradients. clip > 0: clipped MAE, else MSE. Refusals as mlp2_forward_wide.
@@ -1900,6 +1976,8 @@ PYBIND11_MODULE(_C, m) {
   WF_DEF(mlp2_forward_grad_f32);
   WF_DEF(mlp2_path_grad_f32);
   WF_DEF(path_attr);
+  WF_DEF(mlp2_shapley_f32);
+  WF_DEF(mlp2_shapley_scratch_floats);
   m.attr("MLP_F32_ROWS") = wf::kMlpF32Rows;  // the fp32 forward's row tile
   m.attr("MLP_WIDE_ROWS") = wf::kMlpWideRows;  // the wide forward's row tile
   WF_DEF(mlp2_backward);

@@ -272,6 +272,32 @@ bool launch_mlp2_path_grad_f32(const float* X, long ldx, int F, const float* xb,
                                const float* W2, const float* b2, const float* w3, int steps, float* avg, long ldg,
                                int B, hipStream_t s);
 
+// ---- fused fp32 MLP exact Shapley attribution (mlp_f32_shap.hip): per row the Shapley values of
+// the game v(S) = f(own values on the feature spans of S, xb on the other picked spans), for K
+// (1 .. kMlpShapMaxCols) disjoint spans [off[c], off[c] + size[c]) inside [0, F) in source order
+// (HOST arrays) and ONE baseline row xb [F]. coef: HOST fp64 [2][K + 1] = w_in[s], w_out[s]. Layer 1
+// runs K + 1 times per 64-row tile (z0 and one D_c per span) into the workgroup's slab of `scratch`
+// (>= mlp2_shapley_scratch_floats(B, K) floats, 16-B aligned); each of the 2^K coalitions is then
+// a few fp32 adds in descending column index, the 256 x 256 layer and the head, and in ascending
+// coalition index i (bit c of i: column c is own) phi[c][row] = phi + (double)p(S_i) * w, fp64,
+// never contracted, w = w_in[|S|] when c is in S, else -w_out[|S|]. X, W1 .. b3 and B as
+// launch_mlp2_fwd_f32. Writes phi[c * ldo + row], p0[row] = p(no column own), pfull[row] = p(all
+// own) for row < B, p_out[i * ldp + row] when p_out is not null, the scratch slabs, and nothing
+// else (no atomics); a row's result does not depend on B or on its position. Returns nullptr
+// when launched, else the reason (nothing launched).
+constexpr int kMlpShapMaxCols = 12;
+struct ShapleyPlan {  // passed to the kernel by value
+  int K;
+  int off[kMlpShapMaxCols], size[kMlpShapMaxCols];
+  double coef[2][kMlpShapMaxCols + 1];
+};
+size_t mlp2_shapley_scratch_floats(int B, int K);  // 0 for B < 1 or K outside 1 .. kMlpShapMaxCols
+const char* launch_mlp2_shapley_f32(const float* X, long ldx, int F, const float* xb, const float* W1, const float* b1,
+                                    const float* W2, const float* b2, const float* w3, const float* b3, int K,
+                                    const int* off, const int* size, const double* coef, float* scratch,
+                                    size_t scratch_floats, double* phi, long ldo, float* p0, float* pfull, float* p_out,
+                                    long ldp, int B, hipStream_t s);
+
 // ---- fused MLP backward (mlp_fused.hip), everything but the dW2 GEMM: from H1, H2
 // ([B][256] bf16), dy, w3 / W2 and X: dZ2 ([B][256] bf16, dW2's operand), db1, db2, dw3, db3
 // and — when dW1 != nullptr — dW1 ([256][Fp], Fp <= 32) (fp32, accumulated with atomics);

@@ -4,6 +4,7 @@
                                [--repeats R=8] [--columns a,b,..] [--std] [--out PATH] [--seed S] [--device D]
                                [--precision P] [--seq-len T] [--group-col COL] [--batch-size B] [--header]
                                [--method shapley|ig] (ig: [--steps M=32] [--baseline mean|N]; wellflow/integrated.py)
+                               [--method exact] ([--baseline mean|N], at most 12 columns; wellflow/shapley_exact.py)
 
 The prediction, importance and response jobs answer global questions. This one is local: per row
 and per input column a contribution ``phi`` in raw target units which, added to a base value,
@@ -237,22 +238,25 @@ def run_explain(model: str, argv, log=print) -> dict:
         ap.add_argument("--repeats", type=int, default=8, help="sampled column orders / background rows per row (default 8)")
         ap.add_argument("--columns", default=None, help="comma-separated input columns to attribute to (default: all)")
         ap.add_argument("--std", action="store_true", help="also write std_<column>: the spread over the repeats")
-        ap.add_argument("--method", choices=("shapley", "ig"), default="shapley",
-                        help="shapley (sampling, default) or ig (integrated gradients, wellflow/integrated.py)")
+        ap.add_argument("--method", choices=("shapley", "ig", "exact"), default="shapley",
+                        help="shapley (sampling, default), ig (integrated gradients, wellflow/integrated.py) or exact "
+                             "(every coalition of at most 12 columns, wellflow/shapley_exact.py)")
         ap.add_argument("--steps", type=int, default=None, help="ig: midpoint steps along the path (default 32)")
-        ap.add_argument("--baseline", default=None, help="ig: 'mean' (the table's mean feature row, default) or a row number")
+        ap.add_argument("--baseline", default=None,
+                        help="ig, exact: 'mean' (the table's mean feature row, default) or a row number")
 
     ns, cfg, schema, out_path, load_predictor, load_data = scoring_job(
         "explain", "attribution", "explain", "dataPath", model, argv, add_arguments)
-    # which of the two methods' own flags were given: a second parse with every default None, so the
+    # which of the methods' own flags were given: a second parse with every default None, so the
     # parser's own rules (abbreviations, --flag=value) decide, not a scan of the strings
-    own = {"ig": ("steps", "baseline"), "shapley": ("repeats", "std", "seed")}
-    parser[0].set_defaults(**{d: None for ds in own.values() for d in ds})
+    own = {"ig": ("steps", "baseline"), "shapley": ("repeats", "std", "seed"), "exact": ("baseline",)}
+    flags = ("steps", "baseline", "repeats", "std", "seed")
+    parser[0].set_defaults(**{d: None for d in flags})
     probe = parser[0].parse_args(list(argv))
-    for dest in own["shapley" if ns.method == "ig" else "ig"]:
-        if getattr(probe, dest) is not None:
+    for dest in flags:
+        if dest not in own[ns.method] and getattr(probe, dest) is not None:
             raise ValueError(f"--{dest} does not apply to --method {ns.method}")
-    if ns.method == "ig":
+    if ns.method != "shapley":
         return _run_ig(model, ns, cfg, schema, out_path, load_data, log)
     if skipped := other_rank(model, out_path):
         return skipped
@@ -275,10 +279,14 @@ def run_explain(model: str, argv, log=print) -> dict:
 
 def _run_ig(model: str, ns, cfg, schema, out_path: str, load_data, log) -> dict:
     """``--method ig``: integrated gradients (wellflow/integrated.py), through the fused path kernel
-    on a GPU; the model is loaded as the sensitivity job loads it."""
+    on a GPU; ``--method exact``: every coalition (wellflow/shapley_exact.py), through the fused
+    coalition kernel. The model is loaded as the sensitivity job loads it."""
     from .integrated import IntegratedGradients, _note, refuse_model, write_ig_csv
     from .sensitivity import native_precision
 
+    exact = ns.method == "exact"
+    if exact:
+        from .shapley_exact import ExactShapley, refuse_model
     refuse_model(model)  # lstm, cnn: before anything is loaded
     if skipped := other_rank(model, out_path):
         return skipped
@@ -289,14 +297,16 @@ def _run_ig(model: str, ns, cfg, schema, out_path: str, load_data, log) -> dict:
     try:
         pred = load(want)
         if want == "fp32-native" and cfg.precision != want:
-            _note(f"explain: --precision {cfg.precision} is served in fp32 (fp32-native): there is no bf16 path kernel")
+            _note(f"explain: --precision {cfg.precision} is served in fp32 (fp32-native): there is no bf16 "
+                  f"{'coalition' if exact else 'path'} kernel")
     except ValueError as e:
         if want != "fp32-native" or "fp32-native" not in str(e):
             raise
         _note(f"explain: {e}")  # the kernel refuses the shape: the oracle serves it
         pred = load("fp32")
-    job = IntegratedGradients(pred, steps=32 if ns.steps is None else ns.steps,
-                              baseline="mean" if ns.baseline is None else ns.baseline)
+    baseline = "mean" if ns.baseline is None else ns.baseline
+    job = ExactShapley(pred, baseline=baseline) if exact else \
+        IntegratedGradients(pred, steps=32 if ns.steps is None else ns.steps, baseline=baseline)
     table = load_data()
     result = job.run(table, columns=comma_list(ns.columns))
     result["out"] = out_path

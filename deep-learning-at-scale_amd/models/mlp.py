@@ -529,6 +529,49 @@ class NativeMLP(Engine):
                                    out.shape[1], b)
         return out[:b]
 
+    def shapley_f32(self, X: torch.Tensor, baseline: torch.Tensor, off, size, phi: torch.Tensor, row0: int = 0,
+                    p_out: torch.Tensor | None = None) -> tuple:
+        """Exact Shapley values of every row of ``X`` over the ``K`` picked columns whose feature
+        spans are ``[off[c], off[c] + size[c])`` (1 <= K <= 12 ints, source order, disjoint, inside
+        ``[0, F)``), against the ONE row ``baseline``, ONE launch (csrc/mlp_f32_shap.hip): a column
+        outside a coalition takes the baseline's values on its span, unpicked features keep the
+        row's own. ``X`` and ``baseline`` as for :meth:`path_gradients_f32`. ``phi``: a contiguous
+        fp64 ``[K][N]`` tensor on the engine's device, of which ``[:, row0 : row0 + b]`` is written
+        (network units; the rule is ``shapley_exact.exact_shapley_host``). ``p_out``: None, or a
+        contiguous fp32 ``[2^K][>= b]`` tensor that receives every coalition's output. Returns
+        ``(p0[:b], pfull[:b])``, the outputs with no and with every picked column own, in buffers
+        the next call overwrites. No training buffer and not ``pred`` is touched."""
+        from ..shapley_exact import MAX_COLUMNS, shapley_weights
+
+        fn = "shapley_f32"
+        b, ldx = self._f32_rows(fn, X)
+        if not (torch.is_tensor(baseline) and baseline.dtype == torch.float32 and baseline.is_contiguous()):
+            raise ValueError(f"NativeMLP.{fn}: baseline must be a contiguous fp32 tensor (one row)")
+        if baseline.device != self.params.device:
+            raise ValueError(f"NativeMLP.{fn}: baseline is on {baseline.device}, the engine on {self.params.device}")
+        if baseline.numel() < self.F:
+            raise ValueError(f"NativeMLP.{fn}: baseline holds {baseline.numel()} values < {self.F} features")
+        off, size = (torch.as_tensor(v, dtype=torch.int32, device="cpu").reshape(-1).contiguous() for v in (off, size))
+        K = off.numel()
+        if not (1 <= K <= MAX_COLUMNS and size.numel() == K):
+            raise ValueError(f"NativeMLP.{fn}: {K} spans of {size.numel()} sizes (needs the same, 1 .. {MAX_COLUMNS})")
+        if not (torch.is_tensor(phi) and phi.dtype == torch.float64 and phi.dim() == 2 and phi.is_contiguous()
+                and phi.shape[0] == K and phi.device == self.params.device):
+            raise ValueError(f"NativeMLP.{fn}: phi must be a contiguous fp64 [{K}][N] tensor on {self.params.device}")
+        if not 0 <= row0 <= phi.shape[1] - b:
+            raise ValueError(f"NativeMLP.{fn}: rows {row0} .. {row0 + b} are outside phi's {phi.shape[1]}")
+        st = self.__dict__.setdefault("_shap", {})
+        if st.get("K") != K:  # the scratch slabs are sized by K and the engine's batch
+            need = self._C.mlp2_shapley_scratch_floats(self.B, K)
+            st.update(K=K, coef=torch.from_numpy(shapley_weights(K)), scratch=None)
+            st["scratch"] = torch.empty(need, dtype=torch.float32, device=self.params.device)
+            if "p" not in st:
+                st["p"] = torch.empty((2, self.B), dtype=torch.float32, device=self.params.device)
+        pl, hw, hb = self.lay.views(self.params)
+        self._C.mlp2_shapley_f32(X, ldx, self.F, baseline, pl[0][0], pl[0][1], pl[1][0], pl[1][1], hw, hb, off, size,
+                                 st["coef"], st["scratch"], phi, row0, st["p"][0], st["p"][1], p_out, b)
+        return st["p"][0][:b], st["p"][1][:b]
+
     def _recompute_ok(self, B: int) -> bool:
         """The H1-free training step: fused forward writes only the H2 bitmask, the fused
         backward and the dW2 kernel recompute H1 = relu(X W1^T + b1) from X (csrc/mlp_fused.hip)."""

@@ -276,6 +276,27 @@ class MlpPass(_Pass):
                 lib().path_attr(X[c : c + len(g)], g, baseline, F, off, size, phi, a + c)
         return phi
 
+    def exact_attributions(self, baseline: torch.Tensor, off, size) -> tuple:
+        """Exact Shapley values of the table as it is over the columns whose feature spans are
+        ``[off[k], off[k] + size[k])``, against the ONE feature row ``baseline`` (fp32
+        ``[n_features]`` on the device; an fp32-native pass only): per piece and chunk, assemble,
+        then :meth:`NativeMLP.shapley_f32` (csrc/mlp_f32_shap.hip), which writes its columns of
+        the tables in place. Returns the device tables ``(phi fp64 [K][n], p0 fp32 [n])``; ``p``
+        holds the outputs of the table as it is (every picked column own)."""
+        if not (self.native and self.f32):
+            raise ValueError("MlpPass.exact_attributions: the coalition kernel serves the fp32-native pass only")
+        B, dev = self.B, self.p.device
+        phi = torch.empty((len(off), self.M), dtype=torch.float64, device=dev)
+        p0 = torch.empty(self.M, device=dev)
+        host = None if self.on_device else self._features()
+        for a, b in self.pieces:
+            X = self.assemble(a, b, None, host)
+            for c in range(0, b - a, B):  # as forward: [chunk][n_features] slices read in place
+                q0, qf = self.eng.shapley_f32(X[c : c + B], baseline, off, size, phi, a + c)
+                p0[a + c : a + c + len(q0)].copy_(q0)
+                self.p[a + c : a + c + len(qf)].copy_(qf)
+        return phi, p0
+
     def _score_host(self, X: np.ndarray) -> np.ndarray:
         X, B = torch.from_numpy(X), self.B
         p = np.empty(self.M, np.float32)

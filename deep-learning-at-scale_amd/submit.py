@@ -23,6 +23,8 @@ value (``--want-column COL``: one wanted value per row): the inverse of predict 
 
 ``python -m wellflow.submit explain <model> ... --method ig [--steps M] [--baseline mean|N]`` attributes the same
 prediction deterministically with integrated gradients, from the fused fp32 path kernel on a GPU (wellflow/integrated.py).
+``python -m wellflow.submit explain <model> ... --method exact [--baseline mean|N] [--columns a,b,..]`` gives the exact
+Shapley values over at most 12 columns, every coalition from the fused fp32 coalition kernel on a GPU (wellflow/shapley_exact.py).
 
 ``python -m wellflow.submit sensitivity <model> columnNames columnTypes targetColumn storagePath dataPath [--columns a,b,..]``
 writes, per row and continuous input column, the derivative of the prediction (raw target units per raw column
